@@ -10,7 +10,11 @@ Workload of `value` (BASELINE.json configs[1]): Llama-2-7B base + one 1-bit delt
 path, hand-written HIP) + attention / RoPE / SwiGLU (HIP glue of this library) + norm / embedding / lm_head (stock torch).
 N GPUs = N independent replicas (weak scaling, no data-path collective).
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the driver contract fields
+(`value` = prefill tokens/s, `ms_per_step` = milliseconds of one timed step).
+  --dump-outputs DIR   also writes what the last timed step returned (the lm_head logits of the last position) to DIR/logits.npy,
+                       float32; weights and token ids are seeded, so the same arguments give the same inputs on every run
+  --full               after the timed steps also measures the blocks below and prints a "# bench detail" line before the JSON line:
   roofline      the dominant kernel (fused base+delta MFMA GEMM): algorithmic FLOPs of its launches / their summed durations,
                 measured live with HIP events on the launch stream inside the timed region.  `traffic` is null unless THIS run
                 measured it (PMC counters cannot be read in-process; the rocprofv3 passes live under profiles/)
@@ -27,6 +31,7 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus
                 eager and as a hipGraph replay; HBM roofline of its Linear launches
   cpu_baseline  the reference's CPU-executable form of the same projections (oracle/torch_port.py) on all host cores: variant 1
                 (unpack inside the timed region) and variant 2 (pre-unpacked torch.matmul), bounded sample
+  parity        the timed kernels on the timed shapes against the C oracle on sampled columns
 Other workloads: --workload mt-decode (configs[2] / [4] as the main line), --workload tp70b (configs[3], needs --gpus 8).
 """
 import argparse
@@ -712,14 +717,23 @@ def main():
     ap.add_argument("--kv-len", type=int, default=512)
     ap.add_argument("--seq", type=int, default=2048)
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer layers (result is then marked invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="prefill: after the timed steps also measure the fused-launch roofline, the delta-GEMM / vendor-GEMM / MFMA-ceiling / "
+                         "published-shape blocks, the decode legs, the CPU baseline and the parity gate (off: the contract line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="prefill: write what the last timed step returned (the lm_head logits) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity legs")
     ap.add_argument("--ab-glue", action="store_true", help="mt-decode: also time the step with separate RMSNorm / SwiGLU launches")
-    ap.add_argument("--no-mt-decode", action="store_true", help="skip the configs[2] leg of the default run")
+    ap.add_argument("--no-mt-decode", action="store_true", help="--full: skip the decode legs")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:                  # the pinned child of cpu_baseline(): CPU only, prints its JSON object and exits
         print(json.dumps(cpu_baseline_measure(seq=args.seq, reps=args.steps)), flush=True)
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "prefill":
+        ap.error("--dump-outputs is implemented for the prefill workload only")
 
     # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU (the driver's command line
     # may or may not carry the launcher; either way N ranks run, or the run fails -- it never silently measures one rank).
@@ -788,44 +802,87 @@ def main():
 
     from bench_model import Decoder
     args.model = args.model or "llama-2-7b"
+    torch.manual_seed(1234 + rank)          # nn.Embedding / lm_head init and the token ids draw from the default generators: same inputs every run
     model = Decoder(args.model, dev, layers=args.layers, seed=1234 + rank)
     ids = torch.randint(0, model.cfg[5], (1, args.seq), device=dev)
+    last = [None]
 
     def step():
-        return model(ids)
+        last[0] = model(ids)
 
     for _ in range(args.warmup):
         step()
-    # `value`: the K timed steps run CLEAN (no per-launch events inside the region).  The roofline of the dominant kernel is measured
-    # right after, over the same K steps again with every fused launch bracketed by a HIP event pair on the launch stream.
+    # `value`: the K timed steps run CLEAN (no per-launch events inside the region).  With --full the roofline of the dominant kernel is
+    # measured right after, over the same K steps again with every fused launch bracketed by a HIP event pair on the launch stream.
     timer.enabled = False
     dt = bdd.timed_region(step, args.steps, device_sync=torch.cuda.synchronize)
-    timer.enabled = True
-    dt_events = bdd.timed_region(step, args.steps, device_sync=torch.cuda.synchronize)
-    timer.enabled = False
-    torch.cuda.synchronize()
-    n_launch, k_ms, k_flops, k_bytes = timer.summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": last[0]})
+    dt_events = None
+    if args.full:
+        timer.enabled = True
+        dt_events = bdd.timed_region(step, args.steps, device_sync=torch.cuda.synchronize)
+        timer.enabled = False
+        torch.cuda.synchronize()
     tokens = args.seq * args.steps * world
     value = tokens / dt
     n_layers = len(model.layers)
     lin_params = model.linear_param_count()
     model_glue = getattr(model, "glue", "RMSNorm: torch; RoPE, causal attention (bd_srv_prefill_attention), SwiGLU: HIP kernels of this library")
-    del model
+    del model, last
     torch.cuda.empty_cache()
     if rank != 0:
         return
+    out = {
+        "metric": "W1A16 binary-delta GEMM TFLOP/s + tokens/s, Llama-2-7B+Vicuna delta, 1/2/4/8 MI355X "
+                  "(value = end-to-end prefill tokens/s; roofline.delta_gemm = the GEMM figure)",
+        "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"{args.model} base + one 1-bit delta, prefill seq {args.seq}, batch 1 per GPU (BASELINE.json configs[1])",
+                   "launches": f"{n_layers} layers x 4 fused-Linear launches (q|k|v, o, gate|up, down = a layer's 7 BinaryDiff projections)",
+                   "seq_len": args.seq, "global_batch": world, "parallelism": f"dp{world} independent replicas, no collective",
+                   "glue": model_glue, "valid": args.layers is None},
+        **bdd.runtime_info(),
+        "linear_params": lin_params,
+    }
+    if args.full:
+        full_report(args, dev, timer, world, out, dt_events)
+    line = json.dumps(out)
+    if len(line) > 6000:
+        print(f"bench.py: warning: contract line is {len(line)} bytes (> 6000)", file=sys.stderr)
+    print(line, flush=True)
+
+
+def fr(x, nd=4):
+    """numbers of the contract line: 4 decimals for O(1) values, 4 significant digits for small ones; bools / ints / strings untouched"""
+    if isinstance(x, bool) or not isinstance(x, float):
+        return x
+    return round(x, nd) if abs(x) >= 1e-2 or x == 0.0 else float(f"{x:.4g}")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one float32 <path>/<name>.npy per array (64 MB at most in all)."""
+    import numpy as np
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> 64 MB)")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def full_report(args, dev, timer, world, out, dt_events):
+    """--full, rank 0, after the prefill steps: the fused-launch roofline of the events pass, the microbenchmark / calibration blocks, the
+    decode legs, the CPU baseline and the parity gate.  Adds them to the contract line `out` and prints the "# bench detail" line."""
+    n_launch, k_ms, k_flops, k_bytes = timer.summary()
     mb = delta_gemm_microbench(dev)
     vg = vendor_gemm_microbench(dev)
     ceil = mfma_ceiling_block()
     traffic = committed_traffic()
     achieved = k_flops / k_ms * 1e-9 if k_ms > 0 else 0.0
     detail = {"delta_gemm": mb, "vendor_gemm": vg, "mfma_ceiling": ceil, "published_shapes": published_shapes_block(dev)}
-
-    def fr(x, nd=4):
-        """numbers of the contract line: 4 decimals for O(1) values, 4 significant digits for small ones; bools / ints / strings untouched"""
-        if isinstance(x, bool) or not isinstance(x, float):
-            return x
-        return round(x, nd) if abs(x) >= 1e-2 or x == 0.0 else float(f"{x:.4g}")
 
     # The contract line stays SHORT (< 6 KB: the driver's record truncates long lines and keeps only `roofline` / `cpu_baseline` / `config` of the
     # non-contract keys): every figure the north star names sits inside `roofline`; the long blocks go to a "# bench detail" line printed BEFORE it.
@@ -846,20 +903,7 @@ def main():
             "delta_gemm_tflops": {str(r["shape"][0]): fr(r["tflops"], 1) for r in mb},
             "vendor_gemm": {str(r["shape"][0]): fr(r["frac_of_peak"]) for r in vg},
             "mfma_ceiling": {k: fr(v.get("frac_of_peak")) for k, v in ceil.items() if isinstance(v, dict) and "frac_of_peak" in v}}
-    out = {
-        "metric": "W1A16 binary-delta GEMM TFLOP/s + tokens/s, Llama-2-7B+Vicuna delta, 1/2/4/8 MI355X "
-                  "(value = end-to-end prefill tokens/s; roofline.delta_gemm = the GEMM figure)",
-        "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"{args.model} base + one 1-bit delta, prefill seq {args.seq}, batch 1 per GPU (BASELINE.json configs[1])",
-                   "launches": f"{n_layers} layers x 4 fused-Linear launches (q|k|v, o, gate|up, down = a layer's 7 BinaryDiff projections)",
-                   "seq_len": args.seq, "global_batch": world, "parallelism": f"dp{world} independent replicas, no collective",
-                   "glue": model_glue, "valid": args.layers is None},
-        "roofline": roof,
-        **bdd.runtime_info(),
-        "linear_params": lin_params,
-    }
+    out["roofline"] = roof
     single = world == 1 and not args.no_mt_decode
     dec_keys = ("tenants", "valid", "eager_ms_per_step", "hipgraph_ms_per_step", "hipgraph_error", "tokens_per_s", "linear_frac_of_hbm_peak",
                 "step_frac_of_hbm_peak", "norm_handoff")
@@ -910,10 +954,6 @@ def main():
         except Exception as e:
             out["parity"] = {"error": f"{type(e).__name__}: {e}"}
     print("# bench detail (long blocks; the ONE contract line follows): " + json.dumps(detail), flush=True)
-    line = json.dumps(out)
-    if len(line) > 6000:
-        print(f"bench.py: warning: contract line is {len(line)} bytes (> 6000)", file=sys.stderr)
-    print(line, flush=True)
 
 
 if __name__ == "__main__":

@@ -384,7 +384,7 @@ def test_bench_gpus_2_runs_two_ranks_on_one_gpu():
     """bench.py --gpus 2 as the driver invokes it (no launcher): two ranks (gloo control plane, both on the box's one GPU), and the JSON
     line says so: n_gpus == n_ranks_seen == 2."""
     import json
-    r = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "1", "--no-mt-decode", "--no-cpu-baseline"],
+    r = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "1", "--full", "--no-mt-decode", "--no-cpu-baseline"],
                    {"BD_DIST_BACKEND": "gloo"}, 900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

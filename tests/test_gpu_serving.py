@@ -984,7 +984,7 @@ def test_decoder_with_norm_handoff_matches_the_separate_launch_decoder(bd):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("T,M,H", [(1, 2048, 4096), (6, 64, 4096), (3, 100, 2048), (1, 257, 8192), (2, 96, 6144), (1, 70, 4096)])
-def test_rmsnorm_many_rows_kernel_is_bit_identical_to_the_row_per_block_kernel(bd, dtype, T, M, H):
+def test_rmsnorm_many_rows_kernel_is_bit_identical_to_the_row_per_block_kernel(bd, dtype, T, M, H, tmp_path):
     """rmsnorm_rows_kernel (one wave per row, the row in registers; bd_srv_rmsnorm from 64 rows on) forms the four per-wave sums of
     rmsnorm_tenant_kernel with the same lanes in the same order: the two launches must agree BIT FOR BIT (a child process with
     BD_NORM_ROWS_MIN raised runs the block-per-row kernel), on strided rows too, and both match the HF definition"""
@@ -1001,8 +1001,7 @@ def test_rmsnorm_many_rows_kernel_is_bit_identical_to_the_row_per_block_kernel(b
     assert torch.allclose(got.float(), want.float(), rtol=2 ** -7 if dtype == torch.bfloat16 else 2 ** -10, atol=1e-3)
     # the block-per-row kernel in a child process (the dispatch threshold is read once per thread from the environment)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = os.path.join(root, "gpurun_out", f"_norm_ab_{os.getpid()}.pt")
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = str(tmp_path / "norm_ab.pt")
     torch.save({"x": xfull.cpu(), "w": w.cpu(), "H": H}, path)
     code = ("import torch, sys; from bitdelta_amd import serving_ops as ops; d = torch.load(sys.argv[1]); "
             "x = d['x'].cuda()[..., :d['H']]; y = ops.rmsnorm_tenant(x, d['w'].cuda(), 1e-5); torch.save(y.cpu(), sys.argv[1] + '.out')")

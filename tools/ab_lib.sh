@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; A=$1; B=$2; O=gpurun_out/${3:-ab_lib}; mkdi
 for i in 1 2; do
   for tag in A B; do
     lib=$A; [ $tag = B ] && lib=$B
-    BD_HIP_LIB=$PWD/$lib timeout 600 python bench.py --steps 10 --warmup 3 --no-mt-decode --no-cpu-baseline > $O/bench_${tag}${i}.json 2> $O/bench_${tag}${i}.err || tail -3 $O/bench_${tag}${i}.err
+    BD_HIP_LIB=$PWD/$lib timeout 600 python bench.py --steps 10 --warmup 3 --full --no-mt-decode --no-cpu-baseline > $O/bench_${tag}${i}.json 2> $O/bench_${tag}${i}.err || tail -3 $O/bench_${tag}${i}.err
     python3 - $O/bench_${tag}${i}.json $tag$i $lib <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))

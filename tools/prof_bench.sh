@@ -8,7 +8,7 @@ set -u
 OUT=${1:-gpurun_out/prof_bench}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-mt-decode"
+CMD="python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --no-mt-decode"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- $CMD > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o p -- $CMD > /dev/null 2> "$OUT/fetch.err"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o p -- $CMD > /dev/null 2> "$OUT/write.err"

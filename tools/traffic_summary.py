@@ -22,7 +22,7 @@ def per_launch(path, counter, needle):
 
 def bench_summary(fetch_csv, write_csv):
     """--bench: the two kernels the bench line quotes, with their algorithmic bytes"""
-    out = {"note": "HBM/fabric-side bytes per launch from rocprofv3 PMC passes over `python bench.py --steps 3 --warmup 2 --no-cpu-baseline "
+    out = {"note": "HBM/fabric-side bytes per launch from rocprofv3 PMC passes over `python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline "
                    "--no-mt-decode` (FETCH_SIZE and WRITE_SIZE in SEPARATE runs; tools/prof_bench.sh).  bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024: "
                    "FETCH_SIZE reports half of the bytes of wide coalesced streams on gfx950 (MI355X_MICROARCH.md, HBM section).  The counters "
                    "sit on the L2's fabric side, so Infinity-Cache hits are included: an upper bound on DRAM traffic."}
