@@ -523,10 +523,18 @@ int launch_gemv_stream_chunk(const Problem& q) {
         const int fg_tiles = q.N / 16;
         const bool fg_ok = xres_ok && q.N % 16 == 0 && q.t_pad <= 6 && fg_tiles <= 2 * cus &&
                            (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * (2 * (int64_t)q.K + 16) <= STREAM_FG_LDS_MAX;
-        const bool fg = fg_ok && !(g_stream_tune & 256) && ((g_stream_tune & 512) ? true : (STREAM_FG_DEFAULT != 0 && fg_tiles > cus));
+        // Default: resident rows wherever they apply.  (Until the prefetch depths came down to 2 stages this form lost on short launches -- at 6
+        // stages the 4096 x 4096 o projection of a 6-tenant step was +25 % -- and was dispatched by size; at 2 stages it wins on every eligible
+        // launch: 6 tenants 4.805 -> 4.770 ms per step with o included, profiles/r04_decode_step_ab.txt.)  The hand-off consumer needs them
+        // whatever the flags say.
+        const bool xres_auto = STREAM_XRES_DEFAULT != 0;
+        const bool xres = xres_ok && ((g_stream_tune & 64) ? true : (g_stream_tune & 128) ? false : xres_auto);
+        // The fine grid is a resident-row form: decided only for launches that take one (the consumer or `xres`), so a launch that falls
+        // through to the per-stage forms below keeps its own column split (cpb) and LDS layout.  t_last_decode_form is set where an FG
+        // instantiation is launched.
+        const bool fg = fg_ok && (q.ssq_in || xres) && !(g_stream_tune & 256) &&
+                        ((g_stream_tune & 512) ? true : (STREAM_FG_DEFAULT != 0 && fg_tiles > cus));
         const unsigned fg_grid = (unsigned)fg_tiles;
-        if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; }
-        t_last_decode_form = fg ? 1 : 0;
         // Two-pass resident rows (FG = 2, round 6; gemv_stream_kernel): rows that do not fit LDS at once -- the down projection of a multi-tenant
         // step, 6 x 14336 -- with ONE tile per block, every wave's k quarter cut in two halves.  Bit-identical to the per-stage-load form and
         // SLOWER (down 33.0 -> 37.1 us at 2 stages of prefetch, 40.0 at 4; step +4 ... +6 %: profiles/r06_decode_step.txt), so like every A/B
@@ -554,6 +562,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
             // RMSNorm by hand-off (XL = 3): the resident-row form with the rows pre-multiplied by the norm weight and the row scale in the
             // epilogue; same envelope as the resident rows, nothing else implements it
             if (!xres_ok) return BD_E_BAD_SHAPE;
+            if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
 #define BD_XH(NM) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 1, 1, 1>(sp, dim3(fg_grid), q.st)   \
                                              : launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 0, 1, 1>(sp, dim3(fg_grid), q.st))  \
                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 1, 1>(sp, dim3(grid), q.st)   \
@@ -571,12 +580,8 @@ int launch_gemv_stream_chunk(const Problem& q) {
             if (rc != BD_OK) return rc;
             return launch_status();
         }
-        // Default: wherever it applies.  (Until the prefetch depths came down to 2 stages this form lost on short launches -- at 6 stages the
-        // 4096 x 4096 o projection of a 6-tenant step was +25 % -- and was dispatched by size; at 2 stages it wins on every eligible launch:
-        // 6 tenants 4.805 -> 4.770 ms per step with o included, profiles/r04_decode_step_ab.txt.)
-        const bool xres_auto = STREAM_XRES_DEFAULT != 0;
-        const bool xres = xres_ok && ((g_stream_tune & 64) ? true : (g_stream_tune & 128) ? false : xres_auto);
         if (xres) {
+            if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
 #define BD_XR(NM, NS8) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, 1, 1>(sp, dim3(fg_grid), q.st)   \
                                                   : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, 1, 1>(sp, dim3(fg_grid), q.st))  \
                           : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, 1>(sp, dim3(grid), q.st)   \
