@@ -294,7 +294,7 @@ def handoff_ok(B, M, K):
 
 def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=None, groups=1, residual=None,
                          norm_weight=None, eps=1e-5, swiglu=False, weight_tiled=False, out=None, ssq_in=None, ssq_out=None,
-                         xw_out=None, ssq_scale=1.0):
+                         xw_out=None, ssq_scale=1.0, weight_scale=None):
     """binary_linear for decode shapes with repacked masks: one launch of the streaming kernel.
     x: (B, M, K), M <= 16; weight (N, K); alpha fp32 (B or 1, groups);
     layout "tile":   mask = tile_masks(...)        (B or 1, ceil(N/16), K/32, 16)
@@ -309,10 +309,24 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
                copy round(y * norm_weight); ssq_scale multiplies the written sums (serving_loop.handoff_norm: norm_weight = nw / s, ssq_scale = 1 / s^2,
                consumer eps / s^2 -- overflow-safe in fp16, same product);
       ssq_in:  the buffer the PREVIOUS launch filled -- x is that launch's xw_out, 1/rms scales the accumulators: no stand-alone norm launch,
-               no per-block reduction, no multiply (`handoff_ok`); norm_weight must be None."""
-    require_gpu(x, weight, mask, alpha, residual, norm_weight)
+               no per-block reduction, no multiply (`handoff_ok`); norm_weight must be None.
+    INT8 base weight (bd_binary_linear_decode_w8; packed layout, M == 1, N % 16 == 0, K % 128 == 0): weight = quant.tile_weight_int8(CB) (int8,
+      tile-major: there is no row-major int8 form) and weight_scale = SCB / 127 (fp32 [N]); every keyword above keeps its meaning.  The base
+      sum is accumulated on the exactly widened int8 values and multiplied by weight_scale once, in fp32."""
+    require_gpu(x, weight, mask, alpha, residual, norm_weight, weight_scale)
     B, M, K = x.shape
     N = weight.shape[0]
+    w8 = weight.dtype == torch.int8
+    if w8 or weight_scale is not None:
+        if not w8:
+            raise ValueError("weight_scale goes with an int8 weight (quant.tile_weight_int8)")
+        if weight_scale is None:
+            raise ValueError("an int8 base weight needs weight_scale (SCB / 127, fp32 [N])")
+        if not weight_tiled:
+            raise ValueError("the int8 base weight exists in the tile-major decode order only: pass quant.tile_weight_int8(CB), weight_tiled=True")
+        if layout != "packed" or M != 1 or N % 16 or K % 128:
+            raise ValueError("int8 base weight: packed sign layout, one row per tenant, N % 16 == 0, K % 128 == 0")
+        assert weight_scale.dtype == torch.float32 and weight_scale.shape == (N,) and weight_scale.is_contiguous()
     assert mask.dtype == torch.int32 and mask.is_contiguous()
     if layout == "tile":
         assert mask.dim() == 4 and mask.shape[1:] == ((N + 15) // 16, K // 32, 16) and mask.shape[0] in (1, B)
@@ -323,7 +337,7 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
         assert mask.shape[:4] == ((N + 15) // 16, (K + 127) // 128, 4, 16) and B <= mask.shape[4] and B * M <= 16
         code, t_pad = 2, mask.shape[4]
         sPb = 1
-    assert weight.shape[1] == K and weight.stride(1) == 1 and weight.dtype == x.dtype and x.stride(2) == 1
+    assert weight.shape[1] == K and weight.stride(1) == 1 and (w8 or weight.dtype == x.dtype) and x.stride(2) == 1
     out_dtype = out_dtype or x.dtype
     ldw = weight.stride(0)
     if weight_tiled:
@@ -369,10 +383,19 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
         y = out
     else:
         y = torch.empty((B, M, N // 2 if swiglu else N), device=x.device, dtype=out_dtype)
+    if handoff and xw_out is not None:
+        assert xw_out.stride(0) == y.stride(0) and xw_out.stride(1) == y.stride(1), "xw_out uses the output's strides"
+        s_norm = 0 if (norm_weight.shape[0] == 1 and B > 1) else norm_weight.stride(0)
+    if w8:            # one entry point for every launch kind of the int8 base
+        with torch.cuda.device(x.device):
+            check(lib().bd_binary_linear_decode_w8(ptr(x), ptr(weight), ptr(weight_scale), ptr(mask), t_pad, ptr(alpha), ptr(y), B, M, N, K,
+                                                   x.stride(0), x.stride(1), sPb, sAlb, groups, y.stride(0), y.stride(1),
+                                                   DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype], 1 if residual is not None else 0,
+                                                   ptr(norm_weight), s_norm,
+                                                   float(ssq_scale) if ssq_out is not None else float(eps), 1 if swiglu else 0,
+                                                   ptr(ssq_in), ptr(ssq_out), ptr(xw_out), stream_ptr()), "binary_linear_decode_w8")
+        return y
     if handoff:
-        if xw_out is not None:
-            assert xw_out.stride(0) == y.stride(0) and xw_out.stride(1) == y.stride(1), "xw_out uses the output's strides"
-            s_norm = 0 if (norm_weight.shape[0] == 1 and B > 1) else norm_weight.stride(0)
         with torch.cuda.device(x.device):
             check(lib().bd_binary_linear_decode_handoff(ptr(x), ptr(weight), ptr(mask), t_pad, ptr(alpha), ptr(y), B, M, N, K,
                                                         x.stride(0), x.stride(1), ldw, sPb, sAlb, groups, y.stride(0),

@@ -152,7 +152,9 @@ struct Problem {
     int G, dtype, out_dtype, round_mode, accumulate;
     int mask_tiled;           // 0: P is [B or 1, K/32, N] (reference layout); 1: tile-major [B or 1, ceil(N/16), K/32, 16];
                               // 2: packed decode layout [ceil(N/16), ceil(K/128), 4, 16, t_pad] (decode kernel only, see bd_gemv_stream.h)
-    int w_tiled;              // layout 2 only: W is the tile-major decode copy [N/16][K/128][4 steps][16 rows][4 groups][8] (ldw passed as 0)
+    int w_tiled;              // layout 2 only: W is the tile-major decode copy [N/16][K/128][4 steps][16 rows][4 groups][8] (ldw passed as 0);
+                              // 2 = the INT8 tile-major copy of bd_binary_linear_decode_w8, [N/16][K/128][2][16 rows][4 groups][2][8] bytes
+    const float* wscale;      // w_tiled == 2: fp32 [N], multiplies the base sum of each output column
     int t_pad;                // layout 2: dwords per (tile, iteration, lane group, column) = tenants padded to 1 / 2 / 4 / 6 / 8
     const void* norm_w;       // layout 2 only: fused RMSNorm prologue (A is the un-normalised residual stream); [B or 1, K], stride sNw
     int64_t sNw;
@@ -434,9 +436,18 @@ int launch_ring_inst(const RingParams& rp, unsigned grid, hipStream_t st) {
 
 #endif
 
-template <int DT>
+// W8 = 1: the int8 tile-major base weight of bd_binary_linear_decode_w8 (q.w_tiled == 2): the same dispatch rules, the WT = 2 instantiations
+template <int DT, int W8 = 0>
 int launch_gemv_stream_chunk(const Problem& q) {
+    constexpr int WTV = W8 ? 2 : 1;              // gemv_stream_kernel's WT of a tile-major launch
+    // Prefetch depth of the int8 forms: a stage carries HALF the weight bytes, and what saturates HBM is bytes in flight per wave, not stages.
+    // With one or two tenants the int8 launches ran latency-bound at the 16-bit depths and twice the stages put the same bytes in flight
+    // (1 tenant, gate|up 31.3 -> 26.8 us, step 2.55 -> 2.31 ms); from 4 tenants on the sign work bounds the stage, the deeper queue only adds
+    // latency (6 tenants: q|k|v 17.4 -> 18.8 us, o 13.0 -> 14.1) and the norm-prologue form spills: same depth as 16 bits
+    // (rocprofv3 kernel traces, profiles/w8_decode_step.txt).
+#define BD_W8NS(NM, NS) ((W8 && (NM) <= 2) ? 2 * (NS) : (NS))
     StreamParams sp{};
+    sp.wscale = q.wscale;
     t_last_decode_form = 0;
     GemvParams& gp = sp.g;
     gp.X = (const unsigned short*)q.A;
@@ -476,13 +487,13 @@ int launch_gemv_stream_chunk(const Problem& q) {
     sp.x_bytes = (uint32_t)(((int64_t)(q.B - 1) * q.sAb + (int64_t)(q.M - 1) * q.sAm + q.K) * 2);
     sp.w_bytes = q.W ? (uint32_t)(((int64_t)(q.N - 1) * q.ldw + q.K) * 2) : 0u;
     if (q.w_tiled)       // tile-major W: [N/16][K/128] blocks of 4 KiB
-        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * 4096);
+        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * (W8 ? 2048 : 4096));      // (int8: 2 KiB)
     sp.p_bytes = (uint32_t)(((int64_t)(nmask - 1) * q.sPb + (int64_t)(q.K / 32) * (q.mask_tiled ? (q.N + 15) / 16 * 16 : q.N)) * 4);
     int rc;
     if (q.mask_tiled == 2) {      // packed layout: all tenants of the call in one chunk, interleaved; extent from the pack's own geometry
         sp.p_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * 4 * 16 * q.t_pad * 4);
 #ifdef BD_AB_VARIANTS
-        if (ring_wanted()) {      // loader / consumer kernel (variant 700); launches outside its envelope stay on the streaming kernel
+        if (ring_wanted() && !W8) {      // loader / consumer kernel (variant 700); launches outside its envelope stay on the streaming kernel
             RingParams rp{};
             rp.g = gp; rp.cpb = cpb;
             if (ring_plan(q, rp)) {
@@ -540,7 +551,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
         // SLOWER (down 33.0 -> 37.1 us at 2 stages of prefetch, 40.0 at 4; step +4 ... +6 %: profiles/r06_decode_step.txt), so like every A/B
         // loser it exists in harness builds only (-DBD_AB_VARIANTS; bd_set_stream_tuning 8192 = on, + 16384 = 2 stages instead of 4).
 #ifdef BD_AB_VARIANTS
-        const bool fg2 = (g_stream_tune & 8192) && q.w_tiled && !q.norm_w && !q.ssq_in && q.epilogue == 0 && q.M == 1 && q.t_pad <= 8 && q.N % 16 == 0 &&
+        const bool fg2 = (g_stream_tune & 8192) && q.w_tiled == 1 && !q.norm_w && !q.ssq_in && q.epilogue == 0 && q.M == 1 && q.t_pad <= 8 && q.N % 16 == 0 &&
                          fg_tiles <= cus && q.K % 1024 == 0 && q.K >= 8192 && (int64_t)q.B * q.K > 16 * 2048 && (int64_t)q.B * (q.K / 2) <= 24 * 2048 &&
                          (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * ((int64_t)q.K + 16) <= STREAM_LDS_MAX;
         if (fg2) {
@@ -563,17 +574,17 @@ int launch_gemv_stream_chunk(const Problem& q) {
             // epilogue; same envelope as the resident rows, nothing else implements it
             if (!xres_ok) return BD_E_BAD_SHAPE;
             if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
-#define BD_XH(NM) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 1, 1, 1>(sp, dim3(fg_grid), q.st)   \
-                                             : launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 0, 1, 1>(sp, dim3(fg_grid), q.st))  \
-                     : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 1, 1>(sp, dim3(grid), q.st)   \
-                                       : launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 3, 0, 1>(sp, dim3(grid), q.st)
+#define BD_XH(NM) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 1, WTV, 1>(sp, dim3(fg_grid), q.st)   \
+                                             : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 0, WTV, 1>(sp, dim3(fg_grid), q.st))  \
+                     : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 1, WTV>(sp, dim3(grid), q.st)   \
+                                       : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 0, WTV>(sp, dim3(grid), q.st)
             switch (q.t_pad) {
                 case 1: BD_XH(1); break;
                 case 2: BD_XH(2); break;
                 case 4: BD_XH(4); break;
                 case 6: BD_XH(6); break;
-                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 1, 1>(sp, dim3(grid), q.st)
-                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 0, 1>(sp, dim3(grid), q.st); break;
+                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 1, WTV>(sp, dim3(grid), q.st)
+                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 0, WTV>(sp, dim3(grid), q.st); break;
                 default: return BD_E_BAD_SHAPE;
             }
 #undef BD_XH
@@ -582,10 +593,10 @@ int launch_gemv_stream_chunk(const Problem& q) {
         }
         if (xres) {
             if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
-#define BD_XR(NM, NS8) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, 1, 1>(sp, dim3(fg_grid), q.st)   \
-                                                  : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, 1, 1>(sp, dim3(fg_grid), q.st))  \
-                          : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, 1>(sp, dim3(grid), q.st)   \
-                                            : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, 1>(sp, dim3(grid), q.st)
+#define BD_XR(NM, NS8) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, WTV, 1>(sp, dim3(fg_grid), q.st)   \
+                                                  : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, WTV, 1>(sp, dim3(fg_grid), q.st))  \
+                          : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, WTV>(sp, dim3(grid), q.st)   \
+                                            : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, WTV>(sp, dim3(grid), q.st)
             // (A/B, not shipped: the short 6-tenant launches -- q|k|v, o -- on 8-wave blocks, half the stages per wave, are 1 % faster on the
             //  step, 4.688 -> 4.639 ms, but 8 partial sums in another order are no longer bit-identical to every other form of the Linear:
             //  profiles/r04_decode_step_ab.txt.  The kernel template still takes NW = 8 with XL = 2.)
@@ -595,12 +606,12 @@ int launch_gemv_stream_chunk(const Problem& q) {
                 // for this form alone) -- the memory system is saturated by far fewer loads in flight than the register file can hold, and
                 // beyond that point a deeper queue only adds latency (returns are in issue order).  (The parity of NS selects the
                 // activation fragment set, so 2 is the minimum.)
-                case 1: BD_XR(1, 2); break;
-                case 2: BD_XR(2, 2); break;
-                case 4: BD_XR(4, 2); break;
-                case 6: BD_XR(6, 2); break;
-                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 1, 1>(sp, dim3(grid), q.st)
-                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 0, 1>(sp, dim3(grid), q.st); break;
+                case 1: BD_XR(1, BD_W8NS(1, 2)); break;
+                case 2: BD_XR(2, BD_W8NS(2, 2)); break;
+                case 4: BD_XR(4, BD_W8NS(4, 2)); break;
+                case 6: BD_XR(6, BD_W8NS(6, 2)); break;
+                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 1, WTV>(sp, dim3(grid), q.st)
+                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 0, WTV>(sp, dim3(grid), q.st); break;
                 default: return BD_E_BAD_SHAPE;
             }
 #undef BD_XR
@@ -609,12 +620,12 @@ int launch_gemv_stream_chunk(const Problem& q) {
         }
 // (tile-major weight: the norm-prologue forms run 2 stages deep -- 6 tenants: gate|up with its norm at 2 instead of 4 stages is -1 % on
 //  the whole step; the plain / SwiGLU-only forms NS4 stages)
-#define BD_PKW(NM, NS4, AX) (q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, AX, 1, 1, 1, 1>(sp, dim3(grid), q.st)   \
-                                                         : launch_stream_inst<DT, NM, true, 2, 4, 1, AX, 1, 1, 0, 1>(sp, dim3(grid), q.st)) \
-                                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 1, 1>(sp, dim3(grid), q.st)   \
-                                                        : launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 0, 1>(sp, dim3(grid), q.st))
+#define BD_PKW(NM, NS4, AX) (q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, AX, 1, 1, 1, WTV>(sp, dim3(grid), q.st)   \
+                                                         : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, AX, 1, 1, 0, WTV>(sp, dim3(grid), q.st)) \
+                                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 1, WTV>(sp, dim3(grid), q.st)   \
+                                                        : launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 0, WTV>(sp, dim3(grid), q.st))
 #define BD_PK(NM, NS4) rc = q.w_tiled                                                                                                   \
-                     ? (wnt ? BD_PKW(NM, NS4, 2) : BD_PKW(NM, NS4, 0))                                                                  \
+                     ? (wnt ? BD_PKW(NM, BD_W8NS(NM, NS4), 2) : BD_PKW(NM, BD_W8NS(NM, NS4), 0))                                                                \
                      : q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 1>(sp, dim3(grid), q.st)   \
                                                         : launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 0>(sp, dim3(grid), q.st))  \
                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, 0, 1, 0, 1>(sp, dim3(grid), q.st)            \
@@ -631,10 +642,10 @@ int launch_gemv_stream_chunk(const Problem& q) {
             // 9 .. 16 tenants in ONE launch (the reference publishes B = 16: notebooks/binary_gemm_kernel_triton.ipynb:759): plain and SwiGLU
             // launches; the fused-norm / resident-row forms end at 8 rows of K = 4096 anyway
 #define BD_PKL(NM) rc = (q.norm_w || !q.W) ? BD_E_BAD_SHAPE                                                                             \
-                     : q.w_tiled ? (q.epilogue == 1 ? (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 1, 1>(sp, dim3(grid), q.st)    \
-                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 1, 1>(sp, dim3(grid), q.st))  \
-                                                    : (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 0, 1>(sp, dim3(grid), q.st)    \
-                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 0, 1>(sp, dim3(grid), q.st))) \
+                     : q.w_tiled ? (q.epilogue == 1 ? (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 1, WTV>(sp, dim3(grid), q.st)    \
+                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 1, WTV>(sp, dim3(grid), q.st))  \
+                                                    : (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 0, WTV>(sp, dim3(grid), q.st)    \
+                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 0, WTV>(sp, dim3(grid), q.st))) \
                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 1>(sp, dim3(grid), q.st)                     \
                                        : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1>(sp, dim3(grid), q.st)
             case 12: BD_PKL(12); break;
@@ -644,6 +655,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
         }
 #undef BD_PK
 #undef BD_PKW
+#undef BD_W8NS
         if (rc != BD_OK) return rc;
         return launch_status();
     }
@@ -1385,13 +1397,25 @@ extern "C" int bd_delta_bmm(const void* A, const int32_t* P, void* C, int B, int
     return dispatch(q);
 }
 
+// int8 base weight (bd_binary_linear_decode_w8): the streaming decode kernel and nothing else -- a forced variant other than the
+// streaming kernel's own test hooks is refused, like every launch no kernel implements
+static int dispatch_w8(const Problem& q) {
+    if (q.dtype != BD_F16 && q.dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (q.out_dtype != q.dtype && q.out_dtype != BD_F32) return BD_E_BAD_DTYPE;
+    if (q.G < 1 || q.N % q.G) return BD_E_BAD_GROUPS;
+    if (!q.A || !q.P || !q.C || !q.alpha) return BD_E_NULL;
+    if (g_forced_variant >= 0 && !(g_forced_variant >= 600 && g_forced_variant <= 664)) return BD_E_BAD_SHAPE;
+    t_last_variant = 600;
+    return q.dtype == BD_BF16 ? launch_gemv_stream_chunk<DT_BF16, 1>(q) : launch_gemv_stream_chunk<DT_F16, 1>(q);
+}
+
 static int binary_linear_impl(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B, int M,
                               int N, int K, int64_t sXb, int64_t sXm, int64_t ldw, int64_t sPb, int64_t sAlb, int G,
                               int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, int mask_tiled, int t_pad,
                               void* ws, int64_t ws_bytes, void* stream, const void* norm_w = nullptr, int64_t sNw = 0,
                               float eps = 0.f, int epilogue = 0, const float* ssq_in = nullptr, float* ssq_out = nullptr,
                               void* xw_out = nullptr, const void* pn_w = nullptr, int64_t s_pnw = 0, float pn_eps = 0.f, void* pn_h = nullptr,
-                              int64_t sHb = 0, int64_t sHm = 0) {
+                              int64_t sHb = 0, int64_t sHm = 0, const float* wscale = nullptr, bool w8 = false) {
     if (B > 0 && M > 0 && N > 0 && !W) return BD_E_NULL;
     Problem q{};
     q.A = X; q.P = P; q.C = Y; q.W = W; q.alpha = alpha;
@@ -1404,6 +1428,11 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
         if (mask_tiled != 2 || N % 16 || K % 128 || M != 1) return BD_E_BAD_SHAPE;
         q.w_tiled = 1;
         q.ldw = K;            // (extent checks below; the kernel does not use it)
+    }
+    if (w8) {                 // int8 tile-major base weight + row scales: the tile-major envelope, nothing else (no row-major int8 form)
+        if (!q.w_tiled || !wscale || B < 1 || B > GEMV_MAX_R || !aligned16(wscale)) return BD_E_BAD_SHAPE;
+        q.w_tiled = 2;
+        q.wscale = wscale;
     }
     q.norm_w = norm_w; q.sNw = sNw; q.eps = eps; q.epilogue = epilogue;
     q.pn_w = pn_w; q.s_pnw = s_pnw; q.pn_eps = pn_eps; q.pn_h = pn_h; q.sHb = sHb; q.sHm = sHm;
@@ -1452,6 +1481,7 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
     // noise next to the GEMM and stays with the caller)
     // Y += ... (residual epilogue): the decode kernels and the one-pass fused tile kernels (M > 16 on their fast path)
     if (q.accumulate && !gemv_ok(q) && !(M > 16 && fast_ok(q))) return BD_E_BAD_SHAPE;
+    if (q.w_tiled == 2) return dispatch_w8(q);
     return dispatch(q);
 }
 
@@ -1509,6 +1539,18 @@ extern "C" int bd_binary_linear_decode_handoff(const void* X, const void* W, con
     if (B < 1 || M < 1 || N < 1 || K < 1) return BD_E_BAD_SHAPE;
     return binary_linear_impl(X, W, P, alpha, Y, B, M, N, K, sXb, sXm, ldw, sPb, sAlb, G, sYb, sYm, dtype, out_dtype, accumulate, 2,
                               t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out);
+}
+
+extern "C" int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const float* wscale, const int32_t* P, int t_pad, const float* alpha,
+                                          void* Y, int B, int M, int N, int K, int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                                          int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, const void* norm_w,
+                                          int64_t s_norm, float eps, int epilogue, const float* ssq_in, float* ssq_out, void* xw_out,
+                                          void* stream) {
+    if (B < 1 || M != 1 || N < 1 || K < 1 || N % 16 || K % 128) return BD_E_BAD_SHAPE;      // (no row-major int8 form, no M > 1 form)
+    if (!W8 || !wscale) return BD_E_NULL;
+    return binary_linear_impl(X, W8, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
+                              accumulate, 2, t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out, nullptr, 0, 0.f,
+                              nullptr, 0, 0, wscale, true);
 }
 
 extern "C" int bd_binary_linear_residual(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B,

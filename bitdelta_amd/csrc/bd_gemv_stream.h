@@ -84,6 +84,26 @@ __device__ __forceinline__ float scale_then_add(float d, float a, float b) {
     return m + b;
 }
 
+// int8 base weight (WT = 2): 8 consecutive int8 values (two dwords, little-endian) -> one 16-bit MFMA fragment.  Exact: |v| <= 128 needs 8
+// significand bits, fp16 has 11 and bf16 8.  Per weight one byte-select sign-extending convert (v_cvt_f32_i32 with an SDWA source) plus half an
+// instruction of packing: bf16 = the upper half of the fp32 pattern (one v_perm_b32 per pair), fp16 = v_cvt_pkrtz (nothing to round).
+template <int DT> __device__ __forceinline__ uint32_t widen_i8x2(uint32_t v, int j) {
+    const float a = (float)(signed char)(v >> (16 * j)), b = (float)(signed char)(v >> (16 * j + 8));
+    if constexpr (DT == DT_BF16)
+        return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, a), 0x07060302u);
+    else
+        return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
+}
+template <int DT> __device__ __forceinline__ u32x4_t widen_i8x8(uint32_t lo, uint32_t hi) {
+    return u32x4_t{widen_i8x2<DT>(lo, 0), widen_i8x2<DT>(lo, 1), widen_i8x2<DT>(hi, 0), widen_i8x2<DT>(hi, 1)};
+}
+// ... and its per-output-row scale: one fp32 multiply on the reduced base sum, rounded on its own in every epilogue form (see scale_then_add)
+__device__ __forceinline__ f32x4_t scale_base(f32x4_t sb, f32x4_t ws) {
+#pragma clang fp contract(off)
+    const f32x4_t m = sb * ws;
+    return m;
+}
+
 #ifdef BD_STREAM_TRACE
 // s_memtime stamps (harness builds only: tests/native/stream_tl.hip): [block][0] kernel entry, [1] prologue loads issued, [2] first barrier passed,
 // [3] first stage consumed, [4] main loop done, [5] kernel exit; wave 0 of every block
@@ -132,6 +152,8 @@ struct StreamParams {
     // once; exact), xw_out = round16(x . nw / s) can never exceed |x| -- no fp16 overflow on massive-activation rows whatever the norm weight --
     // and ssq_scale = 1 / s^2 together with eps / s^2 on the consumer makes its row scalar s . rsqrt(mean(x^2) + eps): the same product, exactly.
     float ssq_scale;
+    // int8 base weight (WT = 2): wscale[n] = SCB[n] / 127, fp32 [N]; multiplies the base sum of output column n in the epilogue
+    const float* wscale;
 };
 
 // NW = waves per block (8: two per SIMD, 256 VGPRs each; 4: one per SIMD, the whole register file, deeper prefetch).
@@ -175,9 +197,17 @@ struct StreamParams {
 // WT = 1 (packed layout): the base weight is TILE-MAJOR too -- W'[n/16][k/128][s][n%16][g][8] with k = 128 it + 32 s + 8 g + e (the
 //   serving side repacks it once, binary_gemm_kernel.tile_weight): the four load instructions of a stage read four consecutive
 //   1-KiB runs of ONE contiguous 4-KiB block, and a wave's consecutive stages consecutive blocks, instead of 16 rows 2K bytes apart.
+// WT = 2 (packed layout): the base weight is INT8, tile-major, with one fp32 scale per output row (the LLM.int8 vector-wise format the reference
+//   dequantises in bitdelta/misc.py:72-73; bd_binary_linear_decode_w8) -- W8'[n/16][k/128][h][n%16][g][j][8] with k = 128 it + 32 (2 h + j) + 8 g + e
+//   (the serving side repacks it once, quant.tile_weight_int8): one (tile, iteration) stage is ONE contiguous 2-KiB block read by TWO load
+//   instructions of 1 KiB each, and a lane's 16 bytes of load h are exactly its k-octets of MFMA steps 2 h and 2 h + 1 (the 16-bit order
+//   [s][c][g][8] would leave 8-byte pieces).  The bytes are widened to 16 bits in registers (widen_i8x8: exact), one MFMA step ahead of their use
+//   like the sign fragments, so the base accumulator holds exactly what a 16-bit weight equal to CB would give; the row scale multiplies the
+//   REDUCED base sum once, in fp32 (scale_base), before scale_then_add.  Half the weight registers per stage of WT = 1.
 template <int DT, int NM, bool HASW, int NS, int NW = 4, int WNAT = 0, int AUX = 0, int PK = 0, int XL = 0, int EPI = 0, int WT = 0, int FG = 0>
 __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(const StreamParams sp) {
     static_assert(!WT || (PK && HASW), "tile-major W: packed layout");
+    static_assert(WT >= 0 && WT <= 2, "base weight forms: row-major, tile-major 16-bit, tile-major int8");
     static_assert(!FG || (PK && WT && NW == 4 && (XL == 2 || XL == 3)), "fine grid: resident-row forms, packed layout, tile-major W, 256-thread blocks");
     static_assert(FG != 2 || XL == 2, "two-pass rows: the plain resident-row form");
     constexpr int LUTB = stream_lut_bytes(FG);
@@ -270,6 +300,18 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
         }
     }
 
+    // int8 base: the row scales of the four columns this lane stores in the first TWO tiles its wave reduces (tiles wave, wave + NW: every tile of
+    // a block of up to 2 NW tiles -- 128 columns per block, a fused gate|up of 32768 rows on 256 CUs), fetched now for the same reason (one 16-byte
+    // buffer load each: 4 g + e is 16-byte aligned and N % 16 == 0 keeps the quad inside the array; a quad past N reads as zero and is never
+    // stored).  Later tiles of the same wave load theirs in the epilogue, like the residual.
+    [[maybe_unused]] u32x4_t ws_pre[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rws = make_rsrc(WT == 2 ? (const void*)sp.wscale : (const void*)p.X, WT == 2 ? (uint32_t)p.N * 4u : 0u);
+    if constexpr (WT == 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            ws_pre[j] = buf_load16<0>(rws, wave + NW * j < ntile ? (uint32_t)(c_lo + (wave + NW * j) * 16 + 4 * g) * 4u : STREAM_OOB);
+    }
+
     // XL: the R raw rows (and their norm weights) are the OLDEST loads of the wave -- like the scales above, consuming them never
     // waits for a weight stage.  Thread t owns the 16-byte chunks c = 8 t + 2048 i of every row: rmsnorm_tenant_kernel's mapping.
     constexpr int XCH = FG == 2 ? 24 : NW == 8 ? 8 : 16;                 // chunks per thread: R * K <= 16 * 2048 (FG = 2: R * K / 2 <= 24 * 2048; host-checked)
@@ -344,7 +386,7 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    struct Stage { u32x4_t xf[XP ? 4 : 1]; u32x4_t xn[(XN && !XL) ? 4 : 1]; u32x4_t wf[4]; uint32_t wd[NMA]; };
+    struct Stage { u32x4_t xf[XP ? 4 : 1]; u32x4_t xn[(XN && !XL) ? 4 : 1]; u32x4_t wf[WT == 2 ? 2 : 4]; uint32_t wd[NMA]; };
     // one stage = (tile, iteration): 4 x 16 B of the lane's x row, 4 x 16 B of its W row, one sign word per mask
     auto issue = [&](Stage& st, int tile, int it) {
         const int irow = 4 * it + g;                                     // this lane group's word row
@@ -361,11 +403,23 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
             // (the row extents of x and W end at K), except that x rows are contiguous: guard the octet explicitly
             const int k0 = 128 * it + 8 * g;
             const bool it_ok = tile < ntile;
+            if constexpr (HASW && WT == 2) {
+                // int8 tile-major: ONE selected offset for the stage's two 1-KiB runs (load h = steps 2 h, 2 h + 1).  Written per load inside the
+                // loop below, hipcc wrapped the offsets in divergent branches and every stage waited with vmcnt(0) (read in the ISA; the 6-tenant
+                // down projection ran at 46 us against 32 for the 16-bit form).  STREAM_OOB + 1024 is still out of range.
+                const uint32_t wo = (it_ok && it < nit && col_ok)
+                                        ? ((uint32_t)(n >> 4) * (uint32_t)nit + (uint32_t)it) * 2048u + (uint32_t)(n & 15) * 64u + (uint32_t)g * 16u
+                                        : STREAM_OOB;
+                st.wf[0] = buf_load16<AUXW>(rw, wo);
+                st.wf[1] = buf_load16<AUXW>(rw, wo + 1024u);
+            }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bool ok = it_ok && (k0 + 32 * s < p.K);
                 if constexpr (!XL) st.xn[s] = buf_load16<0>(rx, ok ? x_off + (uint32_t)(k0 + 32 * s) * 2u : STREAM_OOB);
-                if constexpr (HASW && WT)
+                if constexpr (HASW && WT == 2) {
+                    // (int8: the two loads of the stage are issued in front of this loop)
+                } else if constexpr (HASW && WT)
                     st.wf[s] = buf_load16<AUXW>(rw, (it_ok && it < nit && col_ok)
                                                        ? ((uint32_t)(n >> 4) * (uint32_t)nit + (uint32_t)it) * 4096u + (uint32_t)s * 1024u +
                                                              (uint32_t)(n & 15) * 64u + (uint32_t)g * 16u
@@ -606,6 +660,11 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
 #pragma unroll
             for (int t = 0; t < NM; ++t) sf[0][t] = lut(cur.wd[t], 0);
         }
+        // int8 base: the 16-bit fragment of step s = the widened k-octet s of the lane's 32 bytes, produced one step ahead (the conversions
+        // issue beside the previous step's MFMAs instead of in front of the base MFMA that needs them)
+        [[maybe_unused]] u32x4_t w8f[2];
+        auto widen = [&](int s) { return widen_i8x8<DT>(cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1)], cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1) + 1]); };
+        if constexpr (WT == 2) w8f[0] = widen(0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if constexpr (SFDB) {
@@ -619,7 +678,10 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
             }
             const u32x4_t xw = XL ? xq[XL ? par : 0][XL ? s : 0] : (XN ? cur.xn[XL ? 0 : s] : cur.xf[XP ? s : 0]);
             const u32x4_t xs_ = XL ? xq[XL ? par : 0][XL ? s : 0] : (PK ? cur.xn[XL ? 0 : s] : cur.xf[XP ? s : 0]);
-            if constexpr (HASW) accB = mfma16<DT>(cur.wf[s], xw, accB);
+            if constexpr (WT == 2) {
+                if (s < 3) w8f[(s + 1) & 1] = widen(s + 1);
+                accB = mfma16<DT>(w8f[s & 1], xw, accB);
+            } else if constexpr (HASW) accB = mfma16<DT>(cur.wf[WT == 2 ? 0 : s], xw, accB);
 #pragma unroll
             for (int t = 0; t < NM; ++t) accD[t] = mfma16<DT>(sf[SFDB ? (s & 1) : 0][t], xs_, accD[t]);
             __builtin_amdgcn_sched_barrier(0);
@@ -658,6 +720,10 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
             for (int w = 0; w < NW; ++w) {                               // fixed wave order: deterministic
                 sb += *(const f32x4_t*)&rb[(w * 64 + lane) * 8];
                 sd += *(const f32x4_t*)&rb[(w * 64 + lane) * 8 + 4];
+            }
+            if constexpr (WT == 2) {                         // int8 base: the row scales of columns 4 g + e of this tile, once, on the reduced sum
+                const u32x4_t wsv = tile == wave ? ws_pre[0] : tile == wave + NW ? ws_pre[1] : buf_load16<0>(rws, (uint32_t)(c_lo + tile * 16 + 4 * g) * 4u);
+                sb = scale_base(sb, __builtin_bit_cast(f32x4_t, wsv));
             }
             if constexpr (EPI == 1) {
                 // tile = [8 gate | 8 up] columns (host: N % 16 == 0, cpb % 16 == 0): lane groups 0,1 hold gate columns 4g + e, groups

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from .binary_gemm_kernel import (binary_linear, binary_linear_residual_norm, binary_linear_swiglu, binary_linear_decode, decode_shape_ok, fused_norm_ok, handoff_ok,
                                  pack_decode_masks, tenant_linear, tile_weight)
+from .quant import dequantize_base_int8, quantize_base_int8, tile_weight_int8, weight_scale
 from .diff import binarize
 from . import serving_ops as ops
 
@@ -72,9 +73,13 @@ class FusedDeltaLinear(nn.Module):
 
     tile_decode_weight = True     # keep a tile-major decode copy of the base weight (class switch)
 
-    def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True):
-        """decode_copies=False skips the decode-only copies (packed sign words, tile-major base weight): a prefill-only user"""
+    def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True, base_int8=False):
+        """decode_copies=False skips the decode-only copies (packed sign words, tile-major base weight): a prefill-only user.
+        base_int8=True: the (concatenated, interleaved) base is quantised once to the LLM.int8 vector-wise format (quant.quantize_base_int8); the
+        16-bit `weight` becomes the reference-dequantised weight (what bitdelta/misc.py dequantize_model leaves in the model: prefill and every
+        M > 1 launch run the unchanged 16-bit kernels on it) and the decode copy is the int8 tile-major weight + one fp32 scale per row."""
         super().__init__()
+        self.base_int8 = bool(base_int8)
         widths = [w.shape[0] for w in weights]
         self.widths = widths
         self.interleave8 = bool(interleave8)
@@ -94,6 +99,13 @@ class FusedDeltaLinear(nn.Module):
                 gsz = math.gcd(gsz, n)
             alpha = torch.cat([c.float().reshape(-1, 1).expand(-1, n // gsz) for c, n in zip(coeffs, widths)], 1)
             self.alpha_pair = None
+        cb = None
+        if self.base_int8:
+            cb, scb = quantize_base_int8(weight)
+            weight = dequantize_base_int8(cb, scb, weight.dtype)
+            self.register_buffer("wscale", weight_scale(scb))
+        else:
+            self.wscale = None
         self.register_buffer("weight", weight.contiguous())
         self.register_buffer("mask", mask.contiguous())
         self.register_buffer("alpha", alpha.contiguous())                                        # [T, G]
@@ -104,7 +116,11 @@ class FusedDeltaLinear(nn.Module):
         # ... and of the base weight in the kernel's tile-major order (one contiguous 4-KiB block per stage; +2 bytes per weight of HBM)
         N, K = self.weight.shape
         tiled = self.mask_packed is not None and self.tile_decode_weight and N % 16 == 0 and K % 128 == 0
-        self.register_buffer("weight_tiled", tile_weight(self.weight) if tiled else None)
+        if self.base_int8:        # the decode copy IS the int8 weight: without it the mode would silently stream 16 bits
+            assert tiled, "base_int8 needs the decode copies: N % 16 == 0, K % 128 == 0, at most 16 tenants"
+            self.register_buffer("weight_tiled", tile_weight_int8(cb))
+        else:
+            self.register_buffer("weight_tiled", tile_weight(self.weight) if tiled else None)
 
     def _decode_ok(self, x):
         B, M, K = x.shape
@@ -123,6 +139,10 @@ class FusedDeltaLinear(nn.Module):
             return self.weight_tiled, True
         return self.weight, False
 
+    def _dec_scale(self, tiled):
+        """weight_scale of a decode launch: the int8 decode copy's row scales (the 16-bit weights take none)"""
+        return self.wscale if (tiled and self.base_int8) else None
+
     use_tiled = True              # (A/B switch)
 
     def forward(self, x, residual=None, out_dtype=None, ssq_out=None, next_norm=None, xw_out=None, out=None, ssq_scale=1.0):
@@ -134,7 +154,8 @@ class FusedDeltaLinear(nn.Module):
             w, wt = self._dec_weight(x)
             return binary_linear_decode(x, w, self.mask_packed, self.alpha, layout="packed", groups=self.groups,
                                         residual=residual, weight_tiled=wt, out_dtype=out_dtype, ssq_out=ssq_out,
-                                        norm_weight=next_norm if ssq_out is not None else None, xw_out=xw_out, out=out, ssq_scale=ssq_scale)
+                                        norm_weight=next_norm if ssq_out is not None else None, xw_out=xw_out, out=out, ssq_scale=ssq_scale,
+                                        weight_scale=self._dec_scale(wt))
         assert ssq_out is None and xw_out is None
         return binary_linear(x, self.weight, self.mask, self.alpha, groups=self.groups, residual=residual, out_dtype=out_dtype, out=out)
 
@@ -170,10 +191,11 @@ class FusedDeltaLinear(nn.Module):
         if swiglu:
             w, wt = self._dec_weight(x)
             return binary_linear_decode(x, w, self.mask_packed, self.alpha_pair, layout="packed", groups=2,
-                                        norm_weight=norm_weight, eps=eps, swiglu=True, weight_tiled=wt, ssq_in=ssq_in)
+                                        norm_weight=norm_weight, eps=eps, swiglu=True, weight_tiled=wt, ssq_in=ssq_in,
+                                        weight_scale=self._dec_scale(wt))
         w, wt = self._dec_weight(x)
         return binary_linear_decode(x, w, self.mask_packed, self.alpha, layout="packed", groups=self.groups,
-                                    norm_weight=norm_weight, eps=eps, weight_tiled=wt, ssq_in=ssq_in)
+                                    norm_weight=norm_weight, eps=eps, weight_tiled=wt, ssq_in=ssq_in, weight_scale=self._dec_scale(wt))
 
     def swiglu_ok(self, x):
         """True when forward_swiglu can take this input: an interleaved gate|up pair at prefill size on the fused GEMM's fast path"""
@@ -197,8 +219,9 @@ class FusedDeltaLinear(nn.Module):
         return self.alpha[t].repeat_interleave(self.weight.shape[0] // self.groups)
 
     def linear_bytes(self):
-        """algorithmic HBM bytes of one decode launch: base once + every tenant's signs (activations / outputs are noise)"""
-        return self.weight.numel() * self.weight.element_size() + self.mask.numel() * 4
+        """algorithmic HBM bytes of one decode launch: base once (one byte per weight in base_int8 mode) + every tenant's signs (activations /
+        outputs / row scales are noise)"""
+        return self.weight.numel() * (1 if self.base_int8 else self.weight.element_size()) + self.mask.numel() * 4
 
 
 def _rope_tables(length, dim, device, dtype, base=10000.0):
@@ -225,8 +248,9 @@ class TenantDecoder(nn.Module):
     MIN_STOP_WIDTH = 8          # stop ids per tenant the static stop table holds before it has to grow (to the next power of two)
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
-    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5):
+    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False):
         super().__init__()
+        self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
         self.cfg, self.T, self.dtype, self.dev, self.eps = cfg, tenants, dtype, torch.device(device), eps
         hid, inter, nl, heads, kvh, vocab = cfg
         self.hd = hid // heads
@@ -280,14 +304,14 @@ class TenantDecoder(nn.Module):
 
     # ---------------------------------------------------------------- construction
     @classmethod
-    def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False):
+    def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
         (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small)."""
         cfg = MODEL_CONFIGS[name] if isinstance(name, str) else tuple(name)
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
-        self = cls(cfg, tenants, device, dtype, max_len=max_len)
+        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -303,7 +327,7 @@ class TenantDecoder(nn.Module):
 
         def fused(*shapes, interleave8=False):
             parts = [delta_linear(o, i) for o, i in shapes]
-            return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8)
+            return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8, base_int8=base_int8)
 
         def per_tenant(*shape, scale=None):
             reps = 1 if shared_heads else tenants

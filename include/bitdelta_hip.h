@@ -155,6 +155,26 @@ int bd_binary_linear_decode_handoff(const void* X, const void* W, const int32_t*
                                     const void* norm_w, int64_t s_norm, float eps, int epilogue,
                                     const float* ssq_in, float* ssq_out, void* xw_out, void* stream);
 
+/* The decode Linear with an INT8 base weight (LLM.int8 vector-wise format: CB int8 [N, K] + SCB = per-output-row absmax; the reference
+ * dequantises it to fp16 with (CB * SCB[:, None]) / 127 and runs the 16-bit path, bitdelta/misc.py:72-73 -- here the bytes stay in HBM and are
+ * widened in registers inside the one launch):
+ *     Y[t, n] = round( wscale[n] * sum_k X[t,k] CB[n,k]  +  alpha[t, g(n)] * sum_k X[t,k] S_t[k,n]  [+ Y_in[t, n]] ),   wscale[n] = SCB[n] / 127
+ * fp32 accumulation, one rounding; the int8 -> 16-bit widening is exact and the row scale multiplies the finished base sum once, in fp32.
+ *   W8: the TILE-MAJOR int8 decode copy (bitdelta_amd.quant.tile_weight_int8), bytes [N/16][K/128][h][16 rows c][4 groups g][j][8] with
+ *       W8'[tile][it][h][c][g][j][e] = CB[16 tile + c][128 it + 32 (2 h + j) + 8 g + e]: one (tile, 128-k) stage = one contiguous 2-KiB block;
+ *   wscale: fp32 [N], 16-byte aligned.
+ * A superset of bd_binary_linear_decode_handoff for that weight form: packed sign layout (t_pad), every argument with the meaning it has there --
+ * norm_w / s_norm / eps (RMSNorm prologue, or the producer's next-norm weight and sum factor), epilogue = 1 (SwiGLU), ssq_in / ssq_out / xw_out
+ * (hand-off), accumulate, fp32 output; all NULL / 0 for the plain launch.  Envelope: M == 1, N % 16 == 0, K % 128 == 0, N >= 512, and what the
+ * tile-major 16-bit weight needs for the same launch kind; anything else -- a row-major int8 weight does not exist -- returns BD_E_BAD_SHAPE.
+ * Arguments are validated before any device work. */
+int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const float* wscale, const int32_t* P, int t_pad, const float* alpha, void* Y,
+                               int B, int M, int N, int K,
+                               int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                               int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate,
+                               const void* norm_w, int64_t s_norm, float eps, int epilogue,
+                               const float* ssq_in, float* ssq_out, void* xw_out, void* stream);
+
 /* the same Linear with the residual connection folded into its epilogue:  Y[b] = Y_in[b] + X[b] . W^T + alpha * (X[b] . S[b])
  * -- the `hidden = residual + o_proj(...)` / `+ down_proj(...)` of the decoder layers that call the reference's modules.
  * Decode shapes (M <= 16, B*M <= 64): fp32 sum, one rounding.  M > 16 on the fused GEMM's fast path (K % 64 == 0, 16-byte aligned
