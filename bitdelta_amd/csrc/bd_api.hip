@@ -59,6 +59,7 @@ static thread_local int g_ring_tune = -1;             // variant 700 knobs, -1 =
                                                       // the ring slots (0 = none)
 static thread_local int t_last_variant = -1;
 static thread_local int t_last_decode_form = 0;    // 1 = the last streaming decode launch took the fine-grid form
+static thread_local int t_last_attention_form = 0; // decode_attn_kernel instantiation of the last launch: nsplit | DEPTH << 8 | MAXS << 16 | G << 24
 
 extern "C" int bd_version(void) { return 1; }
 extern "C" int bd_set_gemm_variant(int v) { g_forced_variant = v; return BD_OK; }
@@ -71,6 +72,7 @@ extern "C" int bd_set_launch_chunking(int on) { g_launch_chunking = on ? 1 : 0; 
 extern "C" int bd_set_decode_generic_loop(int on) { g_col16_no_per4 = on ? 1 : 0; return BD_OK; }
 extern "C" int bd_set_stream_tuning(int flags) { g_stream_tune = flags; return BD_OK; }
 extern "C" int bd_last_decode_form(void) { return t_last_decode_form; }
+extern "C" int bd_last_attention_form(void) { return t_last_attention_form; }
 extern "C" int bd_set_decode_engine(int engine) { g_decode_engine = engine < 0 ? -1 : (engine ? 1 : 0); return BD_OK; }
 extern "C" int bd_set_ring_tuning(int flags) { g_ring_tune = flags; return BD_OK; }
 extern "C" int bd_set_decode_small_lut(int mode) { g_col16_small_lut = mode < 0 ? -1 : (mode ? 1 : 0); return BD_OK; }
@@ -1839,6 +1841,7 @@ extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const
 #define BD_ATT(DT, GG)                                                                                      \
     do {                                                                                                    \
         const bool d2_ = g_attn_depth ? g_attn_depth == 2 : Lc <= 2048;                                                    \
+        t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | (p.nsplit <= 4 ? 4 : 16) << 16 | GG << 24;                 \
         if (p.nsplit <= 4) {                                                                                               \
             if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 4>), grid, dim3(512), 0, st, p);                    \
             else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 4>), grid, dim3(512), 0, st, p);                        \

@@ -72,6 +72,10 @@ int bd_set_stream_tuning(int flags);
  * bits 11 / 12: bd_tenant_linear's weight loads in natural order with (2048) / without (4096) the non-temporal policy (A/B: no difference). */
 /* which form the LAST streaming decode launch of this thread took: 0 = one block per CU, 1 = fine grid, 2 = two-pass resident rows (harness builds) */
 int bd_last_decode_form(void);
+/* which decode_attn_kernel instantiation the LAST bd_srv_decode_attention launch of this thread ran: nsplit | DEPTH << 8 | MAXS << 16 | G << 24
+ * (nsplit = key-range splits, 1 = the unsplit launch; DEPTH = K / V row ring, 2 or 4; MAXS = splits the in-launch merge is written for, 4 or 16;
+ * G = query heads per kv head).  0 before the first launch. */
+int bd_last_attention_form(void);
 /* A/B hook, sign LUT of the no-split-k decode kernel: -1 (default) automatic, 1 = single 4-KiB table, 0 = 16-copy conflict-free
  * 64-KiB table whenever it fits in LDS */
 int bd_set_decode_small_lut(int mode);
