@@ -45,6 +45,8 @@ SIGNATURES = {
                                               _i64, _i64, _ci, _ci, _ci, _vp, _i64, ctypes.c_float, _ci, _vp, _vp, _vp, _vp]),
     "bd_binary_linear_decode_w8": (_ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _ci,
                                          _i64, _i64, _ci, _ci, _ci, _vp, _i64, ctypes.c_float, _ci, _vp, _vp, _vp, _vp]),
+    "bd_binary_linear_decode_q4": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _ci,
+                                         _i64, _i64, _ci, _ci, _ci, _vp, _i64, ctypes.c_float, _ci, _vp, _vp, _vp, _vp]),
     "bd_srv_cache_warm": (_ci, [_vp, _i64, _vp, _i64, _ci, _vp]),
     "bd_srv_step_begin": (_ci, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_step_end": (_ci, [_vp, _i64, _ci, _vp, _vp, _i64, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp]),

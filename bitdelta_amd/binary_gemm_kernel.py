@@ -294,7 +294,7 @@ def handoff_ok(B, M, K):
 
 def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=None, groups=1, residual=None,
                          norm_weight=None, eps=1e-5, swiglu=False, weight_tiled=False, out=None, ssq_in=None, ssq_out=None,
-                         xw_out=None, ssq_scale=1.0, weight_scale=None):
+                         xw_out=None, ssq_scale=1.0, weight_scale=None, group_params=None, group_size=128):
     """binary_linear for decode shapes with repacked masks: one launch of the streaming kernel.
     x: (B, M, K), M <= 16; weight (N, K); alpha fp32 (B or 1, groups);
     layout "tile":   mask = tile_masks(...)        (B or 1, ceil(N/16), K/32, 16)
@@ -312,8 +312,29 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
                no per-block reduction, no multiply (`handoff_ok`); norm_weight must be None.
     INT8 base weight (bd_binary_linear_decode_w8; packed layout, M == 1, N % 16 == 0, K % 128 == 0): weight = quant.tile_weight_int8(CB) (int8,
       tile-major: there is no row-major int8 form) and weight_scale = SCB / 127 (fp32 [N]); every keyword above keeps its meaning.  The base
-      sum is accumulated on the exactly widened int8 values and multiplied by weight_scale once, in fp32."""
-    require_gpu(x, weight, mask, alpha, residual, norm_weight, weight_scale)
+      sum is accumulated on the exactly widened int8 values and multiplied by weight_scale once, in fp32.
+    4-BIT GPTQ base weight (bd_binary_linear_decode_q4; packed layout, M == 1, N % 16 == 0, K % 128 == 0, group_size % 128 == 0):
+      weight = quant.tile_weight_gptq4(qweight) (int32 [N, K/8], tile-major nibbles: there is no row-major 4-bit form), group_params =
+      quant.pack_gptq4_params(qzeros, scales) (int32 [N/16, K/group_size, 16]); every keyword above keeps its meaning.  The nibbles are
+      dequantised in registers to exactly quant.dequantize_base_gptq4(...): the result is the 16-bit launch's on that weight."""
+    q4 = weight.dtype == torch.int32
+    if q4 or group_params is not None:      # (refused here, before anything looks at a device)
+        if not q4:
+            raise ValueError("group_params goes with a 4-bit weight (quant.tile_weight_gptq4)")
+        if group_params is None:
+            raise ValueError("a 4-bit base weight needs group_params (quant.pack_gptq4_params(qzeros, scales))")
+        if weight_scale is not None:
+            raise ValueError("weight_scale belongs to the int8 base weight")
+        if not weight_tiled:
+            raise ValueError("the 4-bit base weight exists in the tile-major decode order only: pass quant.tile_weight_gptq4(qweight), weight_tiled=True")
+        Nq, Kq = weight.shape[0], x.shape[2]
+        if layout != "packed" or x.shape[1] != 1 or Nq % 16 or Kq % 128 or group_size < 128 or group_size % 128 or Kq % group_size:
+            raise ValueError("4-bit base weight: packed sign layout, one row per tenant, N % 16 == 0, K % 128 == 0, group_size a multiple of 128 that divides K")
+        if weight.dim() != 2 or weight.shape[1] * 8 != Kq or not weight.is_contiguous():
+            raise ValueError("4-bit base weight: int32 [N, K/8] as quant.tile_weight_gptq4 returns it")
+        if group_params.dtype != torch.int32 or tuple(group_params.shape) != (Nq // 16, Kq // group_size, 16) or not group_params.is_contiguous():
+            raise ValueError("group_params: int32 [N/16, K/group_size, 16] as quant.pack_gptq4_params returns it")
+    require_gpu(x, weight, mask, alpha, residual, norm_weight, weight_scale, group_params)
     B, M, K = x.shape
     N = weight.shape[0]
     w8 = weight.dtype == torch.int8
@@ -337,7 +358,7 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
         assert mask.shape[:4] == ((N + 15) // 16, (K + 127) // 128, 4, 16) and B <= mask.shape[4] and B * M <= 16
         code, t_pad = 2, mask.shape[4]
         sPb = 1
-    assert weight.shape[1] == K and weight.stride(1) == 1 and (w8 or weight.dtype == x.dtype) and x.stride(2) == 1
+    assert weight.shape[1] == (K // 8 if q4 else K) and weight.stride(1) == 1 and (w8 or q4 or weight.dtype == x.dtype) and x.stride(2) == 1
     out_dtype = out_dtype or x.dtype
     ldw = weight.stride(0)
     if weight_tiled:
@@ -386,6 +407,15 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
     if handoff and xw_out is not None:
         assert xw_out.stride(0) == y.stride(0) and xw_out.stride(1) == y.stride(1), "xw_out uses the output's strides"
         s_norm = 0 if (norm_weight.shape[0] == 1 and B > 1) else norm_weight.stride(0)
+    if q4:            # one entry point for every launch kind of the 4-bit base
+        with torch.cuda.device(x.device):
+            check(lib().bd_binary_linear_decode_q4(ptr(x), ptr(weight), ptr(group_params), int(group_size), ptr(mask), t_pad, ptr(alpha), ptr(y),
+                                                   B, M, N, K, x.stride(0), x.stride(1), sPb, sAlb, groups, y.stride(0), y.stride(1),
+                                                   DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype], 1 if residual is not None else 0,
+                                                   ptr(norm_weight), s_norm,
+                                                   float(ssq_scale) if ssq_out is not None else float(eps), 1 if swiglu else 0,
+                                                   ptr(ssq_in), ptr(ssq_out), ptr(xw_out), stream_ptr()), "binary_linear_decode_q4")
+        return y
     if w8:            # one entry point for every launch kind of the int8 base
         with torch.cuda.device(x.device):
             check(lib().bd_binary_linear_decode_w8(ptr(x), ptr(weight), ptr(weight_scale), ptr(mask), t_pad, ptr(alpha), ptr(y), B, M, N, K,

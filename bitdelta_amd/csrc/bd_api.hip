@@ -157,6 +157,9 @@ struct Problem {
     int w_tiled;              // layout 2 only: W is the tile-major decode copy [N/16][K/128][4 steps][16 rows][4 groups][8] (ldw passed as 0);
                               // 2 = the INT8 tile-major copy of bd_binary_linear_decode_w8, [N/16][K/128][2][16 rows][4 groups][2][8] bytes
     const float* wscale;      // w_tiled == 2: fp32 [N], multiplies the base sum of each output column
+                              // w_tiled == 3: the 4-bit GPTQ tile-major copy of bd_binary_linear_decode_q4, dwords [N/16][K/128][16 rows][4 groups][4 steps]
+    const uint32_t* q4p;      // w_tiled == 3: packed group parameters [N/16][K/q4_group][16] (fp16 scale | fp16 (1024 + z) << 16)
+    int q4_group;             // w_tiled == 3: GPTQ group size along K (a multiple of 128 that divides K)
     int t_pad;                // layout 2: dwords per (tile, iteration, lane group, column) = tenants padded to 1 / 2 / 4 / 6 / 8
     const void* norm_w;       // layout 2 only: fused RMSNorm prologue (A is the un-normalised residual stream); [B or 1, K], stride sNw
     int64_t sNw;
@@ -439,17 +442,30 @@ int launch_ring_inst(const RingParams& rp, unsigned grid, hipStream_t st) {
 #endif
 
 // W8 = 1: the int8 tile-major base weight of bd_binary_linear_decode_w8 (q.w_tiled == 2): the same dispatch rules, the WT = 2 instantiations
+// W8 = 2: the 4-bit GPTQ tile-major base weight of bd_binary_linear_decode_q4 (q.w_tiled == 3): the same rules again, the WT = 3 instantiations
 template <int DT, int W8 = 0>
 int launch_gemv_stream_chunk(const Problem& q) {
-    constexpr int WTV = W8 ? 2 : 1;              // gemv_stream_kernel's WT of a tile-major launch
+    constexpr int WTV = W8 == 2 ? 3 : W8 ? 2 : 1;              // gemv_stream_kernel's WT of a tile-major launch
     // Prefetch depth of the int8 forms: a stage carries HALF the weight bytes, and what saturates HBM is bytes in flight per wave, not stages.
     // With one or two tenants the int8 launches ran latency-bound at the 16-bit depths and twice the stages put the same bytes in flight
     // (1 tenant, gate|up 31.3 -> 26.8 us, step 2.55 -> 2.31 ms); from 4 tenants on the sign work bounds the stage, the deeper queue only adds
     // latency (6 tenants: q|k|v 17.4 -> 18.8 us, o 13.0 -> 14.1) and the norm-prologue form spills: same depth as 16 bits
     // (rocprofv3 kernel traces, profiles/w8_decode_step.txt).
-#define BD_W8NS(NM, NS) ((W8 && (NM) <= 2) ? 2 * (NS) : (NS))
+    // The 4-bit forms follow the same rule with a QUARTER of the weight bytes per stage: one or two tenants run four times the 16-bit depth where
+    // the activation rows are resident (a stage is 3 loads: nibbles, group parameters, signs -- 8 stages keep 21 loads in flight, far inside the
+    // 6-bit vmcnt) and twice where every stage also loads its four activation fragments (7 loads per stage: 4 x 3 stages would need 77 counts);
+    // from 4 tenants on the 16-bit depth, for int8's measured reason.
+#define BD_W8NS(NM, NS) ((W8 && (NM) <= 2) ? (W8 == 2 ? 4 : 2) * (NS) : (NS))
+#define BD_W8NSP(NM, NS) ((W8 && (NM) <= 2) ? 2 * (NS) : (NS))
     StreamParams sp{};
     sp.wscale = q.wscale;
+    if constexpr (W8 == 2) {
+        const uint32_t m = (uint32_t)(q.q4_group / 128);
+        sp.q4p = q.q4p;
+        sp.q4_ngrp = (uint32_t)(q.K / q.q4_group);
+        sp.q4_bytes = (uint32_t)((int64_t)(q.N / 16) * sp.q4_ngrp * 64);
+        sp.q4_magic = m > 1 ? (uint32_t)((1ull << 32) / m) + 1u : 0u;
+    }
     t_last_decode_form = 0;
     GemvParams& gp = sp.g;
     gp.X = (const unsigned short*)q.A;
@@ -489,7 +505,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
     sp.x_bytes = (uint32_t)(((int64_t)(q.B - 1) * q.sAb + (int64_t)(q.M - 1) * q.sAm + q.K) * 2);
     sp.w_bytes = q.W ? (uint32_t)(((int64_t)(q.N - 1) * q.ldw + q.K) * 2) : 0u;
     if (q.w_tiled)       // tile-major W: [N/16][K/128] blocks of 4 KiB
-        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * (W8 ? 2048 : 4096));      // (int8: 2 KiB)
+        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * (W8 == 2 ? 1024 : W8 ? 2048 : 4096));      // (int8: 2 KiB, 4-bit: 1 KiB)
     sp.p_bytes = (uint32_t)(((int64_t)(nmask - 1) * q.sPb + (int64_t)(q.K / 32) * (q.mask_tiled ? (q.N + 15) / 16 * 16 : q.N)) * 4);
     int rc;
     if (q.mask_tiled == 2) {      // packed layout: all tenants of the call in one chunk, interleaved; extent from the pack's own geometry
@@ -627,7 +643,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
                                       : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 1, WTV>(sp, dim3(grid), q.st)   \
                                                         : launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 0, WTV>(sp, dim3(grid), q.st))
 #define BD_PK(NM, NS4) rc = q.w_tiled                                                                                                   \
-                     ? (wnt ? BD_PKW(NM, BD_W8NS(NM, NS4), 2) : BD_PKW(NM, BD_W8NS(NM, NS4), 0))                                                                \
+                     ? (wnt ? BD_PKW(NM, BD_W8NSP(NM, NS4), 2) : BD_PKW(NM, BD_W8NSP(NM, NS4), 0))                                                                \
                      : q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 1>(sp, dim3(grid), q.st)   \
                                                         : launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 0>(sp, dim3(grid), q.st))  \
                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, 0, 1, 0, 1>(sp, dim3(grid), q.st)            \
@@ -658,6 +674,7 @@ int launch_gemv_stream_chunk(const Problem& q) {
 #undef BD_PK
 #undef BD_PKW
 #undef BD_W8NS
+#undef BD_W8NSP
         if (rc != BD_OK) return rc;
         return launch_status();
     }
@@ -1411,13 +1428,25 @@ static int dispatch_w8(const Problem& q) {
     return q.dtype == BD_BF16 ? launch_gemv_stream_chunk<DT_BF16, 1>(q) : launch_gemv_stream_chunk<DT_F16, 1>(q);
 }
 
+// 4-bit GPTQ base weight (bd_binary_linear_decode_q4): as dispatch_w8, the WT = 3 instantiations
+static int dispatch_q4(const Problem& q) {
+    if (q.dtype != BD_F16 && q.dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (q.out_dtype != q.dtype && q.out_dtype != BD_F32) return BD_E_BAD_DTYPE;
+    if (q.G < 1 || q.N % q.G) return BD_E_BAD_GROUPS;
+    if (!q.A || !q.P || !q.C || !q.alpha) return BD_E_NULL;
+    if (g_forced_variant >= 0 && !(g_forced_variant >= 600 && g_forced_variant <= 664)) return BD_E_BAD_SHAPE;
+    t_last_variant = 600;
+    return q.dtype == BD_BF16 ? launch_gemv_stream_chunk<DT_BF16, 2>(q) : launch_gemv_stream_chunk<DT_F16, 2>(q);
+}
+
 static int binary_linear_impl(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B, int M,
                               int N, int K, int64_t sXb, int64_t sXm, int64_t ldw, int64_t sPb, int64_t sAlb, int G,
                               int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, int mask_tiled, int t_pad,
                               void* ws, int64_t ws_bytes, void* stream, const void* norm_w = nullptr, int64_t sNw = 0,
                               float eps = 0.f, int epilogue = 0, const float* ssq_in = nullptr, float* ssq_out = nullptr,
                               void* xw_out = nullptr, const void* pn_w = nullptr, int64_t s_pnw = 0, float pn_eps = 0.f, void* pn_h = nullptr,
-                              int64_t sHb = 0, int64_t sHm = 0, const float* wscale = nullptr, bool w8 = false) {
+                              int64_t sHb = 0, int64_t sHm = 0, const float* wscale = nullptr, bool w8 = false, const uint32_t* q4p = nullptr,
+                              int q4_group = 0) {
     if (B > 0 && M > 0 && N > 0 && !W) return BD_E_NULL;
     Problem q{};
     q.A = X; q.P = P; q.C = Y; q.W = W; q.alpha = alpha;
@@ -1435,6 +1464,12 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
         if (!q.w_tiled || !wscale || B < 1 || B > GEMV_MAX_R || !aligned16(wscale)) return BD_E_BAD_SHAPE;
         q.w_tiled = 2;
         q.wscale = wscale;
+    }
+    if (q4_group) {           // 4-bit GPTQ tile-major base weight + packed group parameters: the tile-major envelope, nothing else
+        if (w8 || !q.w_tiled || !q4p || B < 1 || B > GEMV_MAX_R || !aligned16(q4p) || !aligned16(W)) return BD_E_BAD_SHAPE;
+        if (q4_group < 128 || q4_group % 128 || K % q4_group || K / 128 >= 65536) return BD_E_BAD_SHAPE;
+        q.w_tiled = 3;
+        q.q4p = q4p; q.q4_group = q4_group;
     }
     q.norm_w = norm_w; q.sNw = sNw; q.eps = eps; q.epilogue = epilogue;
     q.pn_w = pn_w; q.s_pnw = s_pnw; q.pn_eps = pn_eps; q.pn_h = pn_h; q.sHb = sHb; q.sHm = sHm;
@@ -1484,6 +1519,7 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
     // Y += ... (residual epilogue): the decode kernels and the one-pass fused tile kernels (M > 16 on their fast path)
     if (q.accumulate && !gemv_ok(q) && !(M > 16 && fast_ok(q))) return BD_E_BAD_SHAPE;
     if (q.w_tiled == 2) return dispatch_w8(q);
+    if (q.w_tiled == 3) return dispatch_q4(q);
     return dispatch(q);
 }
 
@@ -1553,6 +1589,19 @@ extern "C" int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const
     return binary_linear_impl(X, W8, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
                               accumulate, 2, t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out, nullptr, 0, 0.f,
                               nullptr, 0, 0, wscale, true);
+}
+
+extern "C" int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, const uint32_t* qparams, int group_size, const int32_t* P, int t_pad,
+                                          const float* alpha, void* Y, int B, int M, int N, int K, int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb,
+                                          int G, int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, const void* norm_w,
+                                          int64_t s_norm, float eps, int epilogue, const float* ssq_in, float* ssq_out, void* xw_out,
+                                          void* stream) {
+    if (B < 1 || M != 1 || N < 1 || K < 1 || N % 16 || K % 128) return BD_E_BAD_SHAPE;      // (no row-major 4-bit form, no M > 1 form)
+    if (group_size < 128 || group_size % 128 || K % group_size) return BD_E_BAD_SHAPE;      // (a 128-k stage lies inside one group)
+    if (!W4 || !qparams) return BD_E_NULL;
+    return binary_linear_impl(X, W4, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
+                              accumulate, 2, t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out, nullptr, 0, 0.f,
+                              nullptr, 0, 0, nullptr, false, qparams, group_size);
 }
 
 extern "C" int bd_binary_linear_residual(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B,

@@ -104,6 +104,32 @@ __device__ __forceinline__ f32x4_t scale_base(f32x4_t sb, f32x4_t ws) {
     return m;
 }
 
+// 4-bit GPTQ base weight (WT = 3): one qweight dword -- the 8 nibbles of 8 consecutive k of one column -- -> one 16-bit MFMA fragment holding
+// bit for bit what the reference's dequantisation leaves in the model (bitdelta/misc.py:76-105): fp16((q - z) * scale), for bf16 rounded once more.
+// The decode copy stores the nibbles INTERLEAVED (nibble p of the dword = element 2 (p % 4) + p / 4 of the octet), so (v >> 4 d) & 0x000f000f is
+// the element pair (2 d, 2 d + 1) of fragment dword d; or-ing 0x6400 into each half makes it the fp16 number 1024 + q (ulp 1 in [1024, 2048)).
+// zz = the pair (1024 + z, 1024 + z): the packed subtraction gives q - z exactly (an integer in [-16, 14]), the packed multiply by ss = (scale,
+// scale) rounds once, to nearest even, with fp16 subnormals kept -- the reference's one fp16 multiply.  bf16: fp16 -> fp32 is exact and
+// fp32 -> bf16 rounds to nearest even (v_cvt_pk_bf16_f32): the second rounding of `.to(bfloat16)` on the dequantised model.
+// Per element pair: shift, and-or, pk_add, pk_mul (+ two converts and one packing convert for bf16).
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <int DT> __device__ __forceinline__ u32x4_t dequant_q4x8(uint32_t v, uint32_t zz, uint32_t ss) {
+#pragma clang fp contract(off)
+    u32x4_t r;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t h = ((v >> (4 * d)) & 0x000f000fu) | 0x64006400u;
+        const f16x2_t w = (__builtin_bit_cast(f16x2_t, h) - __builtin_bit_cast(f16x2_t, zz)) * __builtin_bit_cast(f16x2_t, ss);
+        if constexpr (DT == DT_BF16)
+            r[d] = __builtin_bit_cast(uint32_t, __builtin_convertvector(__builtin_convertvector(w, f32x2_t), bf16x2_t));
+        else
+            r[d] = __builtin_bit_cast(uint32_t, w);
+    }
+    return r;
+}
+
 #ifdef BD_STREAM_TRACE
 // s_memtime stamps (harness builds only: tests/native/stream_tl.hip): [block][0] kernel entry, [1] prologue loads issued, [2] first barrier passed,
 // [3] first stage consumed, [4] main loop done, [5] kernel exit; wave 0 of every block
@@ -154,6 +180,11 @@ struct StreamParams {
     float ssq_scale;
     // int8 base weight (WT = 2): wscale[n] = SCB[n] / 127, fp32 [N]; multiplies the base sum of output column n in the epilogue
     const float* wscale;
+    // 4-bit GPTQ base weight (WT = 3): the packed group parameters Q[n/16][k/G][n%16], one dword per (tile, group, column): bits 0..15 = the fp16
+    // scale, bits 16..31 = the fp16 number 1024 + z (0x6400 + z, z = 1 .. 16) (quant.pack_gptq4_params).  q4_ngrp = K / G; the group of iteration
+    // `it` is it / (G / 128) = umulhi(it, q4_magic) with q4_magic = floor(2^32 / (G / 128)) + 1 (exact for it < 65536: host-checked), 0 = G is 128
+    const uint32_t* q4p;
+    uint32_t q4_bytes, q4_ngrp, q4_magic;
 };
 
 // NW = waves per block (8: two per SIMD, 256 VGPRs each; 4: one per SIMD, the whole register file, deeper prefetch).
@@ -204,10 +235,18 @@ struct StreamParams {
 //   [s][c][g][8] would leave 8-byte pieces).  The bytes are widened to 16 bits in registers (widen_i8x8: exact), one MFMA step ahead of their use
 //   like the sign fragments, so the base accumulator holds exactly what a 16-bit weight equal to CB would give; the row scale multiplies the
 //   REDUCED base sum once, in fp32 (scale_base), before scale_then_add.  Half the weight registers per stage of WT = 1.
+// WT = 3 (packed layout): the base weight is a 4-BIT GPTQ checkpoint (qweight / qzeros / scales, the format the reference dequantises in
+//   bitdelta/misc.py:76-105; bd_binary_linear_decode_q4), tile-major: dwords W4'[n/16][k/128][n%16][g][s] = qweight[16 it + 4 s + g][n], i.e. the
+//   8 nibbles of k = 128 it + 32 s + 8 g + e of column n, with nibble p of the stored dword = element e = 2 (p % 4) + p / 4 (the serving side
+//   repacks once, quant.tile_weight_gptq4): one (tile, iteration) stage is ONE contiguous 1-KiB block read by ONE load instruction, and a lane's
+//   four dwords are its k-octets of MFMA steps 0 .. 3.  One more dword per stage brings the group parameters of the lane's column
+//   (StreamParams::q4p; a stage is 128 k and G % 128 == 0, so a stage lies in one group).  dequant_q4x8 rebuilds the 16-bit fragment one MFMA step
+//   ahead of its use, bit for bit the reference-dequantised weight: the accumulators hold exactly what a WT = 1 launch on
+//   quant.dequantize_base_gptq4(...) would hold, and the epilogue forms are WT = 1's (no scale).  A quarter of WT = 1's weight registers per stage.
 template <int DT, int NM, bool HASW, int NS, int NW = 4, int WNAT = 0, int AUX = 0, int PK = 0, int XL = 0, int EPI = 0, int WT = 0, int FG = 0>
 __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(const StreamParams sp) {
     static_assert(!WT || (PK && HASW), "tile-major W: packed layout");
-    static_assert(WT >= 0 && WT <= 2, "base weight forms: row-major, tile-major 16-bit, tile-major int8");
+    static_assert(WT >= 0 && WT <= 3, "base weight forms: row-major, tile-major 16-bit, tile-major int8, tile-major 4-bit GPTQ");
     static_assert(!FG || (PK && WT && NW == 4 && (XL == 2 || XL == 3)), "fine grid: resident-row forms, packed layout, tile-major W, 256-thread blocks");
     static_assert(FG != 2 || XL == 2, "two-pass rows: the plain resident-row form");
     constexpr int LUTB = stream_lut_bytes(FG);
@@ -386,7 +425,8 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    struct Stage { u32x4_t xf[XP ? 4 : 1]; u32x4_t xn[(XN && !XL) ? 4 : 1]; u32x4_t wf[WT == 2 ? 2 : 4]; uint32_t wd[NMA]; };
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rq4 = make_rsrc(WT == 3 ? (const void*)sp.q4p : (const void*)p.X, WT == 3 ? sp.q4_bytes : 0u);
+    struct Stage { u32x4_t xf[XP ? 4 : 1]; u32x4_t xn[(XN && !XL) ? 4 : 1]; u32x4_t wf[WT == 2 ? 2 : WT == 3 ? 1 : 4]; uint32_t wd[NMA]; uint32_t gq; };
     // one stage = (tile, iteration): 4 x 16 B of the lane's x row, 4 x 16 B of its W row, one sign word per mask
     auto issue = [&](Stage& st, int tile, int it) {
         const int irow = 4 * it + g;                                     // this lane group's word row
@@ -413,12 +453,24 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
                 st.wf[0] = buf_load16<AUXW>(rw, wo);
                 st.wf[1] = buf_load16<AUXW>(rw, wo + 1024u);
             }
+            if constexpr (HASW && WT == 3) {
+                // 4-bit tile-major: the stage's one 1-KiB run, and the (scale, zero) dword of this lane's column for the stage's group (the four
+                // lane groups of a column read the same dword; default cache policy: G / 128 consecutive stages reuse it)
+                // Both offsets are computed unconditionally and pushed out of range by OR-ing bit 31 in (extents are < 2 GiB): written as two
+                // `ok ? offset : STREAM_OOB` selects, hipcc wrapped the address arithmetic in a divergent branch and every stage waited with
+                // vmcnt(0) -- the int8 form's first bug again (read in the ISA; tests/test_isa_audit_q4.py).
+                const uint32_t oob = (it_ok && it < nit && col_ok) ? 0u : STREAM_OOB;
+                const uint32_t mg = sp.q4_magic;                 // (wave-uniform: scalar multiply-high, no branch)
+                const uint32_t grp = mg ? __umulhi((uint32_t)it, mg) : (uint32_t)it;
+                st.wf[0] = buf_load16<AUXW>(rw, (((uint32_t)(n >> 4) * (uint32_t)nit + (uint32_t)it) * 1024u + (uint32_t)(n & 15) * 64u + (uint32_t)g * 16u) | oob);
+                st.gq = buf_load4<0>(rq4, ((((uint32_t)(n >> 4) * sp.q4_ngrp + grp) * 16u + (uint32_t)(n & 15)) * 4u) | oob);
+            }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bool ok = it_ok && (k0 + 32 * s < p.K);
                 if constexpr (!XL) st.xn[s] = buf_load16<0>(rx, ok ? x_off + (uint32_t)(k0 + 32 * s) * 2u : STREAM_OOB);
-                if constexpr (HASW && WT == 2) {
-                    // (int8: the two loads of the stage are issued in front of this loop)
+                if constexpr (HASW && WT >= 2) {
+                    // (int8 / 4-bit: the weight loads of the stage are issued in front of this loop)
                 } else if constexpr (HASW && WT)
                     st.wf[s] = buf_load16<AUXW>(rw, (it_ok && it < nit && col_ok)
                                                        ? ((uint32_t)(n >> 4) * (uint32_t)nit + (uint32_t)it) * 4096u + (uint32_t)s * 1024u +
@@ -663,8 +715,14 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
         // int8 base: the 16-bit fragment of step s = the widened k-octet s of the lane's 32 bytes, produced one step ahead (the conversions
         // issue beside the previous step's MFMAs instead of in front of the base MFMA that needs them)
         [[maybe_unused]] u32x4_t w8f[2];
-        auto widen = [&](int s) { return widen_i8x8<DT>(cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1)], cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1) + 1]); };
-        if constexpr (WT == 2) w8f[0] = widen(0);
+        // 4-bit base: the same one-step-ahead schedule; the group's (1024 + z, scale) pairs are spread over both halves once per stage
+        [[maybe_unused]] const uint32_t q4z = WT == 3 ? __builtin_amdgcn_perm(cur.gq, cur.gq, 0x03020302u) : 0u;
+        [[maybe_unused]] const uint32_t q4s = WT == 3 ? __builtin_amdgcn_perm(cur.gq, cur.gq, 0x01000100u) : 0u;
+        auto widen = [&](int s) {
+            if constexpr (WT == 3) return dequant_q4x8<DT>(cur.wf[0][s], q4z, q4s);
+            else return widen_i8x8<DT>(cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1)], cur.wf[WT == 2 ? s >> 1 : 0][2 * (s & 1) + 1]);
+        };
+        if constexpr (WT >= 2) w8f[0] = widen(0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if constexpr (SFDB) {
@@ -678,10 +736,10 @@ __global__ void __launch_bounds__(64 * NW, FG == 1 ? 2 : 1) gemv_stream_kernel(c
             }
             const u32x4_t xw = XL ? xq[XL ? par : 0][XL ? s : 0] : (XN ? cur.xn[XL ? 0 : s] : cur.xf[XP ? s : 0]);
             const u32x4_t xs_ = XL ? xq[XL ? par : 0][XL ? s : 0] : (PK ? cur.xn[XL ? 0 : s] : cur.xf[XP ? s : 0]);
-            if constexpr (WT == 2) {
+            if constexpr (WT >= 2) {
                 if (s < 3) w8f[(s + 1) & 1] = widen(s + 1);
                 accB = mfma16<DT>(w8f[s & 1], xw, accB);
-            } else if constexpr (HASW) accB = mfma16<DT>(cur.wf[WT == 2 ? 0 : s], xw, accB);
+            } else if constexpr (HASW) accB = mfma16<DT>(cur.wf[WT >= 2 ? 0 : s], xw, accB);
 #pragma unroll
             for (int t = 0; t < NM; ++t) accD[t] = mfma16<DT>(sf[SFDB ? (s & 1) : 0][t], xs_, accD[t]);
             __builtin_amdgcn_sched_barrier(0);

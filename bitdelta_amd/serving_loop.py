@@ -25,7 +25,8 @@ import torch.nn.functional as F
 
 from .binary_gemm_kernel import (binary_linear, binary_linear_residual_norm, binary_linear_swiglu, binary_linear_decode, decode_shape_ok, fused_norm_ok, handoff_ok,
                                  pack_decode_masks, tenant_linear, tile_weight)
-from .quant import dequantize_base_int8, quantize_base_int8, tile_weight_int8, weight_scale
+from .quant import (cat_gptq4, dequantize_base_gptq4, dequantize_base_int8, pack_gptq4_params, quantize_base_gptq4, quantize_base_int8,
+                    tile_weight_gptq4, tile_weight_int8, weight_scale)
 from .diff import binarize
 from . import serving_ops as ops
 
@@ -73,13 +74,30 @@ class FusedDeltaLinear(nn.Module):
 
     tile_decode_weight = True     # keep a tile-major decode copy of the base weight (class switch)
 
-    def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True, base_int8=False):
+    def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True, base_int8=False, base_gptq4=False, group_size=128,
+                 gptq4=None, dtype=None):
         """decode_copies=False skips the decode-only copies (packed sign words, tile-major base weight): a prefill-only user.
         base_int8=True: the (concatenated, interleaved) base is quantised once to the LLM.int8 vector-wise format (quant.quantize_base_int8); the
         16-bit `weight` becomes the reference-dequantised weight (what bitdelta/misc.py dequantize_model leaves in the model: prefill and every
-        M > 1 launch run the unchanged 16-bit kernels on it) and the decode copy is the int8 tile-major weight + one fp32 scale per row."""
+        M > 1 launch run the unchanged 16-bit kernels on it) and the decode copy is the int8 tile-major weight + one fp32 scale per row.
+        base_gptq4=True (not together with base_int8): the same with the 4-bit GPTQ format, groups of `group_size` (a multiple of 128) along K:
+        the base is quantised once (quant.quantize_base_gptq4), `weight` becomes quant.dequantize_base_gptq4 of it, and the decode copy is the
+        tile-major nibbles + one packed (scale, zero) dword per (group, column).  gptq4 = one (qweight, qzeros, scales) triple per projection (a
+        GPTQ checkpoint) takes the place of the quantiser AND of `weights`, which must then be None: the widths come from the triples, the
+        group size from the checkpoint (K / scales.shape[0]) and `dtype` says what the dequantised weight is cast to.  from_gptq4 spells it."""
         super().__init__()
         self.base_int8 = bool(base_int8)
+        self.base_gptq4 = bool(base_gptq4)
+        self.group_size = int(group_size)
+        assert not (self.base_int8 and self.base_gptq4), "one quantised base form at a time"
+        assert (gptq4 is None or self.base_gptq4) and (gptq4 is None) == (weights is not None), "a checkpoint replaces `weights`"
+        qw = qz = sc = None
+        if gptq4 is not None:             # the 16-bit weight is made once, from the concatenated checkpoint, below
+            dev = masks[0].device
+            widths = [t[0].shape[1] for t in gptq4]
+            qw, qz, sc = cat_gptq4([tuple(u.to(dev) for u in t) for t in gptq4], interleave8=bool(interleave8))
+            self.group_size = qw.shape[0] * 8 // sc.shape[0]
+            weights = [torch.empty(n, 0, device=dev, dtype=dtype or torch.float16) for n in widths]      # (widths, dtype and device only)
         widths = [w.shape[0] for w in weights]
         self.widths = widths
         self.interleave8 = bool(interleave8)
@@ -106,6 +124,14 @@ class FusedDeltaLinear(nn.Module):
             self.register_buffer("wscale", weight_scale(scb))
         else:
             self.wscale = None
+        if self.base_gptq4:
+            if gptq4 is None:
+                qw, qz, sc = quantize_base_gptq4(weight, self.group_size)
+            assert self.group_size % 128 == 0 and (qw.shape[0] * 8) % self.group_size == 0, "group_size: a multiple of 128 that divides K"
+            weight = dequantize_base_gptq4(qw, qz, sc, weight.dtype)
+            self.register_buffer("group_params", pack_gptq4_params(qz, sc) if weight.shape[0] % 16 == 0 else None)
+        else:
+            self.group_params = None
         self.register_buffer("weight", weight.contiguous())
         self.register_buffer("mask", mask.contiguous())
         self.register_buffer("alpha", alpha.contiguous())                                        # [T, G]
@@ -119,8 +145,17 @@ class FusedDeltaLinear(nn.Module):
         if self.base_int8:        # the decode copy IS the int8 weight: without it the mode would silently stream 16 bits
             assert tiled, "base_int8 needs the decode copies: N % 16 == 0, K % 128 == 0, at most 16 tenants"
             self.register_buffer("weight_tiled", tile_weight_int8(cb))
+        elif self.base_gptq4:     # ... or the nibbles
+            assert tiled, "base_gptq4 needs the decode copies: N % 16 == 0, K % 128 == 0, at most 16 tenants"
+            self.register_buffer("weight_tiled", tile_weight_gptq4(qw))
         else:
             self.register_buffer("weight_tiled", tile_weight(self.weight) if tiled else None)
+
+    @classmethod
+    def from_gptq4(cls, triples, masks, coeffs, dtype=torch.float16, interleave8=False, decode_copies=True):
+        """A fused Linear over the projections of a GPTQ checkpoint: triples = [(qweight int32 [K/8, N_i], qzeros int32 [K/G, N_i/8], scales fp16
+        [K/G, N_i]), ...]; masks / coeffs as in __init__.  The group size is the checkpoint's (K / scales.shape[0])."""
+        return cls(None, masks, coeffs, interleave8=interleave8, decode_copies=decode_copies, base_gptq4=True, gptq4=triples, dtype=dtype)
 
     def _decode_ok(self, x):
         B, M, K = x.shape
@@ -143,6 +178,10 @@ class FusedDeltaLinear(nn.Module):
         """weight_scale of a decode launch: the int8 decode copy's row scales (the 16-bit weights take none)"""
         return self.wscale if (tiled and self.base_int8) else None
 
+    def _dec_q4(self, tiled):
+        """group_params / group_size keywords of a decode launch: the 4-bit decode copy's (the other weights take none)"""
+        return dict(group_params=self.group_params, group_size=self.group_size) if (tiled and self.base_gptq4) else {}
+
     use_tiled = True              # (A/B switch)
 
     def forward(self, x, residual=None, out_dtype=None, ssq_out=None, next_norm=None, xw_out=None, out=None, ssq_scale=1.0):
@@ -155,7 +194,7 @@ class FusedDeltaLinear(nn.Module):
             return binary_linear_decode(x, w, self.mask_packed, self.alpha, layout="packed", groups=self.groups,
                                         residual=residual, weight_tiled=wt, out_dtype=out_dtype, ssq_out=ssq_out,
                                         norm_weight=next_norm if ssq_out is not None else None, xw_out=xw_out, out=out, ssq_scale=ssq_scale,
-                                        weight_scale=self._dec_scale(wt))
+                                        weight_scale=self._dec_scale(wt), **self._dec_q4(wt))
         assert ssq_out is None and xw_out is None
         return binary_linear(x, self.weight, self.mask, self.alpha, groups=self.groups, residual=residual, out_dtype=out_dtype, out=out)
 
@@ -192,10 +231,11 @@ class FusedDeltaLinear(nn.Module):
             w, wt = self._dec_weight(x)
             return binary_linear_decode(x, w, self.mask_packed, self.alpha_pair, layout="packed", groups=2,
                                         norm_weight=norm_weight, eps=eps, swiglu=True, weight_tiled=wt, ssq_in=ssq_in,
-                                        weight_scale=self._dec_scale(wt))
+                                        weight_scale=self._dec_scale(wt), **self._dec_q4(wt))
         w, wt = self._dec_weight(x)
         return binary_linear_decode(x, w, self.mask_packed, self.alpha, layout="packed", groups=self.groups,
-                                    norm_weight=norm_weight, eps=eps, weight_tiled=wt, ssq_in=ssq_in, weight_scale=self._dec_scale(wt))
+                                    norm_weight=norm_weight, eps=eps, weight_tiled=wt, ssq_in=ssq_in, weight_scale=self._dec_scale(wt),
+                                    **self._dec_q4(wt))
 
     def swiglu_ok(self, x):
         """True when forward_swiglu can take this input: an interleaved gate|up pair at prefill size on the fused GEMM's fast path"""
@@ -219,8 +259,10 @@ class FusedDeltaLinear(nn.Module):
         return self.alpha[t].repeat_interleave(self.weight.shape[0] // self.groups)
 
     def linear_bytes(self):
-        """algorithmic HBM bytes of one decode launch: base once (one byte per weight in base_int8 mode) + every tenant's signs (activations /
-        outputs / row scales are noise)"""
+        """algorithmic HBM bytes of one decode launch: base once (one byte per weight in base_int8 mode; half a byte plus the 4-byte group
+        parameters in base_gptq4 mode) + every tenant's signs (activations / outputs / row scales are noise)"""
+        if self.base_gptq4:
+            return self.weight.numel() // 2 + self.group_params.numel() * 4 + self.mask.numel() * 4
         return self.weight.numel() * (1 if self.base_int8 else self.weight.element_size()) + self.mask.numel() * 4
 
 
@@ -248,8 +290,9 @@ class TenantDecoder(nn.Module):
     MIN_STOP_WIDTH = 8          # stop ids per tenant the static stop table holds before it has to grow (to the next power of two)
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
-    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False):
+    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False):
         super().__init__()
+        self.base_gptq4 = bool(base_gptq4)  # ... or a 4-bit GPTQ base (FusedDeltaLinear(base_gptq4=True)); lm_head, embeddings and norms stay 16-bit
         self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
         self.cfg, self.T, self.dtype, self.dev, self.eps = cfg, tenants, dtype, torch.device(device), eps
         hid, inter, nl, heads, kvh, vocab = cfg
@@ -304,14 +347,15 @@ class TenantDecoder(nn.Module):
 
     # ---------------------------------------------------------------- construction
     @classmethod
-    def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False):
+    def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
+                  base_gptq4=False):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
         (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small)."""
         cfg = MODEL_CONFIGS[name] if isinstance(name, str) else tuple(name)
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
-        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8)
+        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -327,7 +371,8 @@ class TenantDecoder(nn.Module):
 
         def fused(*shapes, interleave8=False):
             parts = [delta_linear(o, i) for o, i in shapes]
-            return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8, base_int8=base_int8)
+            return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8, base_int8=base_int8,
+                                    base_gptq4=base_gptq4)
 
         def per_tenant(*shape, scale=None):
             reps = 1 if shared_heads else tenants

@@ -175,6 +175,28 @@ int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const float* wsc
                                const void* norm_w, int64_t s_norm, float eps, int epilogue,
                                const float* ssq_in, float* ssq_out, void* xw_out, void* stream);
 
+/* The decode Linear with a 4-BIT GPTQ base weight (qweight int32 [K/8, N], qzeros int32 [K/G, N/8], scales fp16 [K/G, N]; no g_idx): the
+ * reference dequantises it to fp16 with (q - z) * scale, z = stored nibble + 1, and runs the 16-bit path (bitdelta/misc.py:76-105) -- here the
+ * nibbles stay in HBM and are dequantised in registers inside the one launch, bit for bit to the weight Wdq the reference leaves in the model
+ * (fp16((q - z) * scale); for bf16 rounded once more):
+ *     Y[t, n] = round( sum_k X[t,k] Wdq[n,k]  +  alpha[t, g(n)] * sum_k X[t,k] S_t[k,n]  [+ Y_in[t, n]] )
+ * fp32 accumulation, one rounding: the value a tile-major 16-bit launch on Wdq gives.
+ *   W4: the TILE-MAJOR nibble decode copy (bitdelta_amd.quant.tile_weight_gptq4), dwords [N/16][K/128][16 rows c][4 groups g][4 steps s] with
+ *       W4'[tile][it][c][g][s] = qweight[16 it + 4 s + g][16 tile + c], the 8 nibbles of k = 128 it + 32 s + 8 g + e, stored interleaved:
+ *       nibble p of the dword = element e = 2 (p % 4) + p / 4.  One (tile, 128-k) stage = one contiguous 1-KiB block; 16-byte aligned;
+ *   qparams: the packed group parameters (bitdelta_amd.quant.pack_gptq4_params), dwords [N/16][K/G][16 rows c]: bits 0..15 the fp16 scale,
+ *       bits 16..31 the fp16 number 1024 + z (0x6400 + z, z = 1 .. 16), of column 16 tile + c in that group; 16-byte aligned;
+ *   group_size: G, a multiple of 128 that divides K.
+ * Otherwise bd_binary_linear_decode_w8's argument list, every argument with the meaning it has there.  Envelope: M == 1, N % 16 == 0,
+ * K % 128 == 0, G % 128 == 0, N >= 512, at most 16 tenants, and what the tile-major 16-bit weight needs for the same launch kind; anything
+ * else returns BD_E_BAD_SHAPE.  Arguments are validated before any device work. */
+int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, const uint32_t* qparams, int group_size, const int32_t* P, int t_pad,
+                               const float* alpha, void* Y, int B, int M, int N, int K,
+                               int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                               int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate,
+                               const void* norm_w, int64_t s_norm, float eps, int epilogue,
+                               const float* ssq_in, float* ssq_out, void* xw_out, void* stream);
+
 /* the same Linear with the residual connection folded into its epilogue:  Y[b] = Y_in[b] + X[b] . W^T + alpha * (X[b] . S[b])
  * -- the `hidden = residual + o_proj(...)` / `+ down_proj(...)` of the decoder layers that call the reference's modules.
  * Decode shapes (M <= 16, B*M <= 64): fp32 sum, one rounding.  M > 16 on the fused GEMM's fast path (K % 64 == 0, 16-byte aligned

@@ -3,9 +3,9 @@
 
     python tools/ab_decode_step.py --tenants 6 --arms base:0 fg_off:256 fg_all:512 pf:0:prefetch
 
-An arm is name:stream_tuning_flags[:prefetch|nostep|int8] (options joined with +).  `int8` arms run on a decoder whose delta Linears stream an
+An arm is name:stream_tuning_flags[:prefetch|nostep|int8|gptq4] (options joined with +).  `int8` arms run on a decoder whose delta Linears stream an
 int8 base (TenantDecoder.synthetic(..., base_int8=True)), e.g. `--arms w16:0 w8:0:int8 w16b:0` -- the third arm is an A/A twin of the first and
-gives the run's own noise.  Each arm is captured as its own graph (dispatch decisions are taken at capture time);
+gives the run's own noise; `gptq4` arms stream a 4-bit GPTQ base (base_gptq4=True), e.g. `--arms w16:0 q4:0:gptq4 w8:0:int8 w16b:0`.  Each arm is captured as its own graph (dispatch decisions are taken at capture time);
 the arms are then timed alternately, `--rounds` rounds of `--steps` replays each; min and median per arm are printed.
 Replaces the one-off tools/gpu_r4*.sh / gpu_r5*.sh scripts of earlier rounds for this kind of question."""
 import argparse
@@ -35,11 +35,11 @@ def main():
     T = args.tenants
     ctxs = {}
 
-    def context(int8):
+    def context(base):
         """one decoder + prefilled request state per base form, shared by the arms of that form (same seed: the same 16-bit base and deltas)"""
-        if int8 not in ctxs:
+        if base not in ctxs:
             dec = TenantDecoder.synthetic(args.model, T, dev, dtype=torch.float16, seed=4321, layers=args.layers, max_len=args.kv_len + 256,
-                                          base_int8=int8)
+                                          base_int8=base == "int8", base_gptq4=base == "gptq4")
             vocab = dec.cfg[5]
             g = torch.Generator().manual_seed(4321)
             prompts = [torch.randint(1, vocab, (args.kv_len,), generator=g).tolist() for _ in range(T)]
@@ -56,8 +56,8 @@ def main():
                 for k, v in snap.items():
                     st[k].copy_(v)
                 cache["valid"].copy_(valid0)
-            ctxs[int8] = (dec, st, restore)
-        return ctxs[int8]
+            ctxs[base] = (dec, st, restore)
+        return ctxs[base]
 
     runners, toks, form, restores = {}, {}, {}, {}
     for arm in args.arms:
@@ -66,8 +66,8 @@ def main():
         opts = parts[2] if len(parts) > 2 else ""
         if args.replay_only and name != args.replay_only:
             continue
-        form[name] = "int8" if "int8" in opts else "w16"
-        dec, st, restore = context("int8" in opts)
+        form[name] = "int8" if "int8" in opts else "gptq4" if "gptq4" in opts else "w16"
+        dec, st, restore = context(form[name])
         restores[name] = restore
         dec.prefetch_o = "prefetch" in opts
         dec.step_kernels = "nostep" not in opts          # (stock torch ops at both ends of the step)
@@ -103,8 +103,8 @@ def main():
             ms[n].append(bdd.timed_region(run, args.steps, device_sync=torch.cuda.synchronize) / args.steps * 1e3)
     names = list(runners)
     first_of = {f: next(n for n in names if form[n] == f) for f in set(form.values())}
-    bytes_ = {f: [int(b) for b in ctxs[f == "int8"][0].linear_bytes_per_step()] for f in set(form.values())}
-    out = {"model": args.model, "tenants": T, "kv_len": args.kv_len, "layers": len(ctxs[form[names[0]] == "int8"][0].layers), "steps": args.steps,
+    bytes_ = {f: [int(b) for b in ctxs[f][0].linear_bytes_per_step()] for f in set(form.values())}
+    out = {"model": args.model, "tenants": T, "kv_len": args.kv_len, "layers": len(ctxs[form[names[0]]][0].layers), "steps": args.steps,
            "linear_bytes_per_step": bytes_,
            "arms": {n: {"base": form[n], "min_ms": min(v), "median_ms": sorted(v)[len(v) // 2], "all_ms": [round(x, 4) for x in v],
                         "tokens_equal_first_arm": bool(torch.equal(toks[n], toks[first_of[form[n]]]))} for n, v in ms.items()}}
