@@ -50,9 +50,12 @@ SIGNATURES = {
     "bd_srv_cache_warm": (_ci, [_vp, _i64, _vp, _i64, _ci, _vp]),
     "bd_srv_step_begin": (_ci, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_step_end": (_ci, [_vp, _i64, _ci, _vp, _vp, _i64, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp]),
+    "bd_srv_step_begin_ragged": (_ci, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "bd_srv_step_end_ragged": (_ci, [_vp, _i64, _ci, _vp, _vp, _i64, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_rope_kv_append": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_rope": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_decode_attention": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),
+    "bd_srv_decode_attention_ragged": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),
     "bd_srv_decode_attention_workspace_bytes": (_i64, [_ci, _ci, _ci, _ci, _ci]),
     "bd_srv_prefill_attention": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                        _vp, ctypes.c_float, _ci, _ci, _vp]),

@@ -1819,6 +1819,38 @@ extern "C" int bd_srv_step_end(const void* logits, int64_t sl, int V, int64_t* t
     return launch_status();
 }
 
+extern "C" int bd_srv_step_begin_ragged(const void* embed, int64_t sEt, int64_t sEv, const int64_t* tok, void* X, int64_t sx, void* valid, int Lc,
+                                        const int64_t* pos, const void* active, int T, int V, int H, void* stream) {
+    if (T < 0 || V < 1 || H < 1 || Lc < 1) return BD_E_BAD_SHAPE;
+    if (T == 0) return BD_OK;
+    if (!embed || !tok || !X || !valid || !pos || !active) return BD_E_NULL;
+    if (H % 8 || sEv % 8 || sEt % 8 || sx % 8 || sEv < H || sx < H || sEt < 0 || !aligned16(embed) || !aligned16(X)) return BD_E_BAD_SHAPE;
+    hipLaunchKernelGGL(step_begin_ragged_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)embed, (long long)sEt,
+                       (long long)sEv, (const long long*)tok, (unsigned short*)X, (long long)sx, (unsigned char*)valid, Lc, (const long long*)pos,
+                       (const unsigned char*)active, V, H);
+    return launch_status();
+}
+
+extern "C" int bd_srv_step_end_ragged(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
+                                      const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done,
+                                      int Lc, int T, int dtype, void* stream) {
+    if (T < 0 || V < 1 || ns < 0 || out_cap < 0 || Lc < 1) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (T == 0) return BD_OK;
+    if (!logits || !tok || !out || !pos || !n || !limit || !active || !done || (ns > 0 && !stop_ids)) return BD_E_NULL;
+    if (V % 8 || sl % 8 || sl < V || s_out < out_cap || !aligned16(logits)) return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == BD_BF16)
+        hipLaunchKernelGGL((step_end_ragged_kernel<DT_BF16>), dim3((unsigned)T), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           (long long*)tok, (long long*)out, (long long)s_out, out_cap, (const long long*)stop_ids, ns, (long long*)pos,
+                           (long long*)n, (const long long*)limit, (unsigned char*)active, (unsigned char*)done, Lc);
+    else
+        hipLaunchKernelGGL((step_end_ragged_kernel<DT_F16>), dim3((unsigned)T), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           (long long*)tok, (long long*)out, (long long)s_out, out_cap, (const long long*)stop_ids, ns, (long long*)pos,
+                           (long long*)n, (const long long*)limit, (unsigned char*)active, (unsigned char*)done, Lc);
+    return launch_status();
+}
+
 extern "C" int bd_srv_cache_warm(const void* p0, int64_t bytes0, const void* p1, int64_t bytes1, int blocks, void* stream) {
     if (bytes0 < 0 || bytes1 < 0 || blocks < 0) return BD_E_BAD_SHAPE;
     if ((bytes0 && !p0) || (bytes1 && !p1)) return BD_E_NULL;
@@ -1855,19 +1887,23 @@ extern "C" int64_t bd_srv_decode_attention_workspace_bytes(int T, int H, int KVH
     return ATTN_TICKET_BYTES + (int64_t)T * H * ATTN_SPLITS_MAX * (head_dim + 2) * 4;      // (sized for the largest split count: independent of the A/B hook)
 }
 
-extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
-                                       void* valid, const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
-                                       int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
+// bd_srv_decode_attention and its ragged form: ONE body, so validation, split rule, workspace layout and depth rule cannot drift apart (a ragged
+// launch at equal positions has the scalar launch's geometry).  RAGGED: pos is [T] and `active` [T] bytes.
+template <bool RAGGED>
+static int decode_attention_launch(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
+                                   void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                   int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
     if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (T == 0) return BD_OK;
-    if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !valid || !pos || !out) return BD_E_NULL;
+    if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !valid || !pos || !out || (RAGGED && !active)) return BD_E_NULL;
     const int G = H / KVH;
     if (head_dim != 128 || (G != 1 && G != 4 && G != 8) || s_qkv % 8 || !aligned16(QKV) || !aligned16(kcache) || !aligned16(vcache))
         return BD_E_BAD_SHAPE;                         // other head geometries: the caller keeps its torch attention
     AttnParams p;
     p.qkv = (const unsigned short*)QKV; p.cos = (const unsigned short*)cos_t; p.sin = (const unsigned short*)sin_t;
     p.kc = (unsigned short*)kcache; p.vc = (unsigned short*)vcache; p.valid = (unsigned char*)valid; p.pos = (const long long*)pos;
+    p.active = (const unsigned char*)active;
     p.out = (unsigned short*)out; p.T = T; p.H = H; p.KVH = KVH; p.Lc = Lc; p.s_qkv = s_qkv; p.s_out = s_out;
     p.scale = 1.0f / sqrtf((float)head_dim);
     // split the key range over 4 blocks per (tenant, kv head) when the cache is long enough and a workspace is given: T * KVH blocks
@@ -1892,11 +1928,11 @@ extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const
         const bool d2_ = g_attn_depth ? g_attn_depth == 2 : Lc <= 2048;                                                    \
         t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | (p.nsplit <= 4 ? 4 : 16) << 16 | GG << 24;                 \
         if (p.nsplit <= 4) {                                                                                               \
-            if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 4>), grid, dim3(512), 0, st, p);                    \
-            else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 4>), grid, dim3(512), 0, st, p);                        \
+            if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 4, RAGGED>), grid, dim3(512), 0, st, p);                    \
+            else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 4, RAGGED>), grid, dim3(512), 0, st, p);                        \
         } else {                                                                                                           \
-            if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 16>), grid, dim3(512), 0, st, p);                   \
-            else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 16>), grid, dim3(512), 0, st, p);                       \
+            if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 16, RAGGED>), grid, dim3(512), 0, st, p);                   \
+            else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 16, RAGGED>), grid, dim3(512), 0, st, p);                       \
         }                                                                                                                  \
     } while (0)
     // G = query heads per kv head: 1 (Llama-2-7B), 4 (Mistral-7B), 8 (Llama-2-70B -- also per rank under tensor parallelism).
@@ -1906,6 +1942,20 @@ extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const
     else { if (G == 1) BD_ATT(DT_F16, 1); else if (G == 4) BD_ATT(DT_F16, 4); else BD_ATT(DT_F16, 8); }
 #undef BD_ATT
     return launch_status();
+}
+
+extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
+                                       void* valid, const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                       int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
+    return decode_attention_launch<false>(QKV, cos_t, sin_t, kcache, vcache, valid, pos, nullptr, out, T, H, KVH, head_dim, Lc, s_qkv, s_out, dtype,
+                                          ws, ws_bytes, stream);
+}
+
+extern "C" int bd_srv_decode_attention_ragged(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
+                                              void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim,
+                                              int Lc, int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
+    return decode_attention_launch<true>(QKV, cos_t, sin_t, kcache, vcache, valid, pos, active, out, T, H, KVH, head_dim, Lc, s_qkv, s_out, dtype,
+                                         ws, ws_bytes, stream);
 }
 
 extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,

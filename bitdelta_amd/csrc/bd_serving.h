@@ -341,6 +341,73 @@ __global__ void __launch_bounds__(256) step_end_kernel(const unsigned short* __r
     }
 }
 
+// The ragged forms of the two ends of the step (TenantSession, serving_loop.py): every tenant has its OWN position pos[t], token count n[t],
+// limit[t] and activity byte active[t], so a tenant is admitted while the others are mid-generation and retires at its own stop token.  An
+// inactive tenant, or one whose position lies outside the cache (device data the host never sees advance), gets a zero row -- finite through
+// RMSNorm and every Linear -- and no mark.
+__global__ void __launch_bounds__(256) step_begin_ragged_kernel(const unsigned short* __restrict__ embed, long long sEt, long long sEv,
+                                                                const long long* __restrict__ tok, unsigned short* __restrict__ x, long long sx,
+                                                                unsigned char* __restrict__ valid, int Lc, const long long* __restrict__ pos,
+                                                                const unsigned char* __restrict__ active, int V, int H) {
+    const int t = blockIdx.x;
+    const long long p = pos[t];
+    const bool live = active[t] != 0 && p >= 0 && p < Lc;
+    long long id = tok[t];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    const unsigned short* row = embed + (long long)t * sEt + id * sEv;
+    const u32x4_t zero = {0u, 0u, 0u, 0u};
+    for (int c = threadIdx.x * 8; c < H; c += 256 * 8) *(u32x4_t*)(x + (long long)t * sx + c) = live ? *(const u32x4_t*)(row + c) : zero;
+    if (threadIdx.x == 0 && live) valid[(long long)t * Lc + p] = 1;
+}
+
+// One block per tenant, no ticket and no shared counter: a tenant's block is the only one that touches its state.  Inactive tenants touch
+// nothing.  reason bits: 1 = stop token, 2 = n reached limit, 4 = the cache is full.
+template <int DT>
+__global__ void __launch_bounds__(256) step_end_ragged_kernel(const unsigned short* __restrict__ logits, long long sl, int V, long long* __restrict__ tok,
+                                                              long long* __restrict__ out, long long s_out, int out_cap,
+                                                              const long long* __restrict__ stop_ids, int ns, long long* __restrict__ pos,
+                                                              long long* __restrict__ n, const long long* __restrict__ limit,
+                                                              unsigned char* __restrict__ active, unsigned char* __restrict__ done, int Lc) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int t = blockIdx.x;
+    if (active[t] == 0) return;                                         // uniform over the block
+    const unsigned short* row = logits + (long long)t * sl;
+    float best = -__builtin_inff();
+    int bidx = 0x7fffffff;
+    for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
+        const u32x4_t v = *(const u32x4_t*)(row + c);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const float lo = half_bits_to_f32<DT>(v[d] & 0xffffu), hi = half_bits_to_f32<DT>(v[d] >> 16);
+            if (argmax_better(lo, c + 2 * d, best, bidx)) { best = lo; bidx = c + 2 * d; }
+            if (argmax_better(hi, c + 2 * d + 1, best, bidx)) { best = hi; bidx = c + 2 * d + 1; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bidx, off, 64);
+        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = bidx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (argmax_better(bv[w], bi[w], best, bidx)) { best = bv[w]; bidx = bi[w]; }
+        const long long nxt = bidx, n0 = n[t], n1 = n0 + 1, p1 = pos[t] + 1;
+        tok[t] = nxt;
+        if (n0 >= 0 && n0 < out_cap) out[(long long)t * s_out + n0] = nxt;
+        n[t] = n1;
+        pos[t] = p1;
+        int reason = 0;
+        for (int j = 0; j < ns; ++j) reason |= (stop_ids[(long long)t * ns + j] == nxt) ? 1 : 0;
+        reason |= (n1 >= limit[t] ? 2 : 0) | (p1 >= Lc ? 4 : 0);
+        if (reason) { active[t] = 0; done[t] = (unsigned char)reason; }
+    }
+}
+
 // In-place rotary embedding of [rows, heads * 128] (a q or k projection output before the head transpose), HF rotate-half form with
 // the sign folded into `sin`: out[d] = round16(round16(x[d] * cos[d]) + x[d +- 64] * sin[d])  -- the rounding points of the stock
 // composition `torch.addcmul(x * cos, rot, sin)`, which costs five passes (cat, mul, addcmul + two temporaries) instead of one.
@@ -436,7 +503,8 @@ struct AttnParams {
     unsigned short* kc;            // KV cache [T, KVH, Lc, 128]
     unsigned short* vc;
     unsigned char* valid;          // [T, Lc] key-validity bytes (left padding = 0); the new position is set here
-    const long long* pos;          // device scalar: cache position of the new token
+    const long long* pos;          // device scalar: cache position of the new token (RAGGED: [T], one position per tenant)
+    const unsigned char* active;   // RAGGED only: [T] activity bytes; a tenant with active[t] == 0 stays out of the launch
     unsigned short* out;           // [T, H * 128]
     int T, H, KVH, Lc;
     long long s_qkv, s_out;        // row strides (elements)
@@ -460,7 +528,13 @@ __device__ __forceinline__ float attn_ws_load(const float* src) {
 
 // MAXS = key-range splits per (tenant, kv head) the in-launch merge is written for (host: nsplit <= MAXS): 4, or 16 for launches with few
 // (tenant, kv head) pairs -- a single sequence on 8 kv heads is 32 blocks at 4 splits
-template <int DT, int G, int DEPTH = 4, int MAXS = 4>
+// RAGGED (TenantSession): tenant t's position is pos[t] -- the key range, the split geometry, the RoPE row, the append and the mark are its own --
+// and a block whose tenant is inactive or whose position lies outside [0, Lc) stays out: zeros to its G * 128 outputs, no append, no mark, no
+// partial, no ticket (all splits of a pair read the same pos[t] / active[t], which nothing writes during the launch, so the tickets' zero-at-
+// enqueue / zero-at-exit contract holds).  pos[t] is a scalar load like *pos; the position is CLAMPED for addressing and the activity byte is
+// only looked at after the ring is in flight, so neither a dependent load nor a branch sits in front of the ring (a block that stays out has
+// fetched row 0 of its own cache for nothing).  RAGGED = false is the kernel as it was.
+template <int DT, int G, int DEPTH = 4, int MAXS = 4, bool RAGGED = false>
 __global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
     constexpr int ATTN_MAX_SPLITS = MAXS;
     constexpr int HD = 128, NWV = 8, RPI = 4 * NWV;
@@ -470,7 +544,21 @@ __global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
     __shared__ float a_lds[NWV][G][HD];
     const int t = blockIdx.x / p.KVH, kvh = blockIdx.x % p.KVH;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long pos = *p.pos;
+    long long pos;
+    unsigned char act = 1;
+    bool in_cache = true;
+    if constexpr (RAGGED) {
+        const long long pt = p.pos[t];
+        // the activity byte through the SCALAR path, next to pos[t]: the aligned dword that holds it (a byte load is a vector load, whose result
+        // the compiler moved to an SGPR behind a vmcnt(0) of its own, in front of everything)
+        const uintptr_t ab = (uintptr_t)(p.active + t);
+        typedef const __attribute__((address_space(4))) uint32_t* const_word_ptr;     // (constant address space: nothing writes it during the launch)
+        act = (unsigned char)(*(const_word_ptr)(ab & ~(uintptr_t)3) >> (8 * (ab & 3)));
+        in_cache = pt >= 0 && pt < p.Lc;
+        pos = in_cache ? pt : 0;
+    } else {
+        pos = *p.pos;
+    }
     const unsigned short* row = p.qkv + (long long)t * p.s_qkv;
     const unsigned short* cs = p.cos + pos * HD;
     const unsigned short* sn = p.sin + pos * HD;
@@ -512,6 +600,14 @@ __global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
     Rows ring[DEPTH];
 #pragma unroll
     for (int u = 0; u < DEPTH; ++u) load_row(l_lo + (long long)u * RPI + slot, ring[u]);
+    if constexpr (RAGGED) {
+        asm volatile("" ::: "memory");                   // (keeps the ring's loads in front of the branch)
+        if (!(in_cache && act != 0)) {                // uniform over the block, and over the splits of its (tenant, kv head) pair
+            if (blockIdx.y == 0)
+                for (int i = threadIdx.x; i < G * HD; i += 64 * NWV) p.out[(long long)t * p.s_out + (long long)kvh * G * HD + i] = 0;
+            return;
+        }
+    }
 
     // ---- phase 0: RoPE of the G query heads and of the new key (torch: round16(round16(x*cos) + rot*sin)), cache append
     auto rope_bits = [&](unsigned short xb, unsigned short xrb, unsigned short cb, unsigned short sb) {

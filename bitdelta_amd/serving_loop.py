@@ -247,6 +247,18 @@ class FusedDeltaLinear(nn.Module):
         """act_fn(gate_proj(x)) * up_proj(x) of the MLP in ONE launch at prefill size (bd_binary_linear_swiglu): [B, M, inter]"""
         return binary_linear_swiglu(x, self.weight, self.mask, self.alpha_pair)
 
+    def tenant_view(self, t):
+        """This Linear for tenant t alone, on the SAME storage: the base weight whole, mask / alpha / alpha_pair sliced [t:t+1].  No decode copies
+        (they interleave the tenants), so it serves prompts (more than 16 rows), which is what a one-tenant prefill runs."""
+        v = FusedDeltaLinear.__new__(FusedDeltaLinear)
+        nn.Module.__init__(v)
+        v.base_int8, v.base_gptq4, v.group_size = self.base_int8, self.base_gptq4, self.group_size
+        v.widths, v.interleave8, v.groups = self.widths, self.interleave8, self.groups
+        v.weight, v.mask, v.alpha = self.weight, self.mask[t:t + 1], self.alpha[t:t + 1]
+        v.alpha_pair = self.alpha_pair[t:t + 1] if self.alpha_pair is not None else None
+        v.wscale = v.group_params = v.mask_packed = v.weight_tiled = None
+        return v
+
     def split(self, y):
         """per-projection outputs of y = forward(x)  (undoes the interleaved row order)"""
         if self.interleave8:
@@ -323,6 +335,7 @@ class TenantDecoder(nn.Module):
         self._static = {}               # (stop-table width, glue switches) -> static request state + captured decode-step graph (LRU)
         self._kv_cache = None           # ONE KV cache per decoder, shared by every slot
         self._capture_stream = None
+        self._tenant_views = {}         # tenant -> one-tenant view of this decoder (tenant_view)
         self.fuse_qkv_norm = False      # RMSNorm folded into the q|k|v launch
         # RMSNorm folded into the gate|up launch (SwiGLU stays in its epilogue either way): every block re-normalises all rows (rows + norm
         # weights from L2) to save one ~4.5 us launch.  Same-process A/Bs at the end of round 4, with the resident-row form (which needs no
@@ -438,11 +451,12 @@ class TenantDecoder(nn.Module):
             setattr(layer, key, v)
         return v
 
-    def _layer(self, layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid=False, next_layer=None, h_in=None):
+    def _layer(self, layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid=False, next_layer=None, h_in=None, ragged=None):
         """one decoder layer; returns (x, ssq_valid): whether self._ssq / self._xw hold the partial sums of squares of the returned x and its
         copy pre-multiplied by the NEXT layer's input norm weight (next_layer; None after the last layer) -- both in handoff_norm's scaled form.
         h_in: norm1 of x when the previous layer's down projection already produced it (prefill, forward_residual_norm); the third return value is
-        that tensor for the next layer (or None)."""
+        that tensor for the next layer (or None).  ragged: (pos [T], active [T]) of a TenantSession step -- one position per tenant; pos_idx is
+        then not looked at."""
         T, S, hid = x.shape
         _, inter, _, heads, kvh, _ = self.cfg
         hd = self.hd
@@ -471,7 +485,12 @@ class TenantDecoder(nn.Module):
             with torch.cuda.stream(pf):
                 w_o = layer.o.weight_tiled if (layer.o.weight_tiled is not None and layer.o.use_tiled) else layer.o.weight
                 ops.cache_warm(w_o, layer.o.mask_packed)
-        if S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd):
+        if ragged is not None:
+            # a session's step: the same launch with each tenant at its own position; there is no stock-op form of it to fall to
+            if not (S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd)):
+                raise RuntimeError("a ragged decode step needs the HIP decode attention (fast_glue, head_dim 128, 1 / 4 / 8 query heads per kv head)")
+            a = ops.decode_attention_ragged(qkv, self.cos, self.sin, ck, cv, cache["valid"], ragged[0], ragged[1], heads, kvh)
+        elif S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd):
             # decode: RoPE + cache append + attention over the valid keys in ONE launch (pos_idx is a one-element device tensor)
             a = ops.decode_attention(qkv, self.cos, self.sin, ck, cv, cache["valid"], pos_idx, heads, kvh)
         elif (S > 1 and self.fast_glue and cache.get("kv_start") is not None and hd == 128 and S % 64 == 0 and qkv.is_contiguous()
@@ -541,15 +560,17 @@ class TenantDecoder(nn.Module):
         return x, d_hand, None
 
     @torch.no_grad()
-    def forward(self, ids, pos_idx, cache, attn_mask, x=None):
+    def forward(self, ids, pos_idx, cache, attn_mask, x=None, ragged=None):
         """ids [T, S]; pos_idx [S] (device, positions of these tokens in the cache); attn_mask [T, 1, S, L] bool.
-        Returns the logits of the LAST position, [T, vocab].  x: the embedded tokens when the caller already has them (step_begin)."""
+        Returns the logits of the LAST position, [T, vocab].  x: the embedded tokens when the caller already has them (step_begin).
+        ragged=(pos [T], active [T]): one decode token per tenant, each at its own position (TenantSession); pos_idx and attn_mask are unused."""
         T, S = ids.shape
         _, _, _, heads, kvh, _ = self.cfg
+        assert ragged is None or S == 1
         # (the rows of the rotary tables are gathered only for the stock-op attention paths: the HIP kernels index the tables themselves)
         hip_attn = self.fast_glue and ((S == 1 and ops.decode_attention_supported(heads, kvh, self.hd)) or
                                        (S > 1 and cache.get("kv_start") is not None and self.hd == 128 and S % 64 == 0))
-        cos, sin = (None, None) if hip_attn else (self.cos[pos_idx], self.sin[pos_idx])
+        cos, sin = (None, None) if (hip_attn or ragged is not None) else (self.cos[pos_idx], self.sin[pos_idx])
         if x is None:
             t_idx = torch.arange(T, device=ids.device).view(T, 1)
             x = self.embed[t_idx, ids]                                        # per-tenant embedding: one gather
@@ -557,7 +578,7 @@ class TenantDecoder(nn.Module):
         h_in = None
         for li, layer in enumerate(self.layers):
             nxt = self.layers[li + 1] if li + 1 < len(self.layers) else None
-            x, ssq_valid, h_in = self._layer(layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid, nxt, h_in)
+            x, ssq_valid, h_in = self._layer(layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid, nxt, h_in, ragged=ragged)
         last = self._norm(x[:, -1:, :], self.final_norm)
         return tenant_linear(last, self.lm_head)[:, 0, :]                     # per-tenant lm_head: one launch
 
@@ -684,6 +705,39 @@ class TenantDecoder(nn.Module):
             n += 1
         return st["out"][:, :n].cpu(), n
 
+    # ---------------------------------------------------------------- per-tenant requests
+    _SWITCHES = ("fast_glue", "swiglu_epilogue", "short_prompt_fusions", "hip_prefill_attention", "fuse_glue")
+
+    def tenant_view(self, t):
+        """A one-tenant TenantDecoder over tenant t's slices of THIS decoder's tensors -- sign words, scales, embedding, norms, lm_head; the base
+        weights whole -- for prefilling one tenant alone.  Nothing is copied: every tensor of the view is the parent's storage, offset by the
+        tenant.  It carries no decode copies (packed sign words, tile-major weights): it is a prefill-only user."""
+        assert 0 <= t < self.T
+        views = self._tenant_views
+        v = views.get(t)
+        if v is None:
+            v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4)
+            v.cos, v.sin = self.cos, self.sin
+            for layer in self.layers:
+                lv = nn.Module()
+                for name in ("qkv", "o", "gate_up", "down"):
+                    setattr(lv, name, getattr(layer, name).tenant_view(t))
+                lv.norm1, lv.norm2 = layer.norm1[t:t + 1], layer.norm2[t:t + 1]
+                v.layers.append(lv)
+            v.embed, v.final_norm, v.lm_head = self.embed[t:t + 1], self.final_norm[t:t + 1], self.lm_head[t:t + 1]
+            views[t] = v
+        for name in self._SWITCHES:
+            setattr(v, name, getattr(self, name))
+        return v
+
+    def cache_view(self, cache, t):
+        """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
+        return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
+
+    def session(self, max_stop_ids=8):
+        """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step."""
+        return TenantSession(self, max_stop_ids)
+
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
         step (4 Linear launches + ~20 small torch ops per layer) replays without per-op host overhead."""
@@ -706,3 +760,164 @@ class TenantDecoder(nn.Module):
             st[k].copy_(v)
         st["cache"]["valid"].copy_(snap_valid)
         return g.replay
+
+
+class TenantSession:
+    """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
+    own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
+    Linear launches over the same T rows -- with the three launches that knew a shared position replaced by their ragged forms
+    (serving_ops.step_begin_ragged / decode_attention_ragged / step_end_ragged): every tenant has its own pos / n / limit / active / done on the
+    device.  An inactive tenant's row runs through the step as zeros and none of its state, cache rows or validity bytes is touched.
+
+    Greedy, one sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
+    it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
+    reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full; 0 = still active or never submitted."""
+
+    def __init__(self, dec, max_stop_ids=8):
+        _, _, _, heads, kvh, _ = dec.cfg
+        if not (dec.fast_glue and dec.step_kernels):
+            raise ValueError("a session runs on the HIP glue and step kernels (fast_glue, step_kernels); there is no stock-op ragged step")
+        if not ops.decode_attention_supported(heads, kvh, dec.hd):
+            raise ValueError("a session needs the HIP decode attention: head_dim 128 and 1, 4 or 8 query heads per kv head")
+        if dec.embed.shape[-1] % 8 or dec.lm_head.shape[-2] % 8:
+            raise ValueError("a session needs hidden and vocabulary sizes that are multiples of 8 (the step kernels' 16-byte rows)")
+        if dec.prefetch_o:
+            raise ValueError("a session does not take prefetch_o=True (a side branch in the captured step)")
+        self.dec, self.T, dev = dec, dec.T, dec.dev
+        if dec._kv_cache is None:
+            dec._kv_cache = dec.new_cache()
+        self.cache = dec._kv_cache
+        self.Lc = self.cache["valid"].shape[1]
+        T = self.T
+        self.tok = torch.zeros(T, 1, dtype=torch.long, device=dev)
+        self.pos = torch.zeros(T, dtype=torch.long, device=dev)
+        self.n = torch.zeros(T, dtype=torch.long, device=dev)
+        self.limit = torch.zeros(T, dtype=torch.long, device=dev)
+        self.active_flags = torch.zeros(T, dtype=torch.bool, device=dev)
+        self.done = torch.zeros(T, dtype=torch.uint8, device=dev)
+        self.stop_ids = torch.full((T, max(int(max_stop_ids), 1)), -1, dtype=torch.long, device=dev)
+        self.out = torch.zeros(T, dec.max_len, dtype=torch.long, device=dev)      # (a caller may swap in a strided view BEFORE the first step)
+        self._graphs = {}
+
+    # ------------------------------------------------------------ admission
+    def _stops(self, stop_token_ids):
+        s_ = sorted(int(i) for i in (stop_token_ids or ()))
+        if len(s_) > self.stop_ids.shape[1]:
+            raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
+        return s_
+
+    def _admit(self, t, first, L, max_new_tokens, stops):
+        """tenant t's state after its prefill: the first token is the prefill's argmax"""
+        reason = (1 if first in stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
+        self.stop_ids[t].fill_(-1)
+        if stops:
+            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long, device=self.dec.dev)
+        self.out[t].zero_()
+        self.out[t, 0] = first
+        self.tok[t, 0] = first
+        self.n[t] = 1
+        self.pos[t] = L
+        self.limit[t] = int(max_new_tokens)
+        self.done[t] = reason
+        self.active_flags[t] = reason == 0
+
+    @torch.no_grad()
+    def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=()):
+        """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
+        padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
+        alone through tenant_view(t), and the tenant starts at its own position."""
+        dec = self.dec
+        assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
+        if bool(self.active_flags[t]):
+            raise RuntimeError("tenant %d is still generating" % t)
+        L = padded_length(len(prompt))
+        if L > MAX_PROMPT:
+            raise ValueError("max_len too large, please reduce the input length")
+        if L > self.Lc:
+            raise ValueError("the padded prompt does not fit the KV cache")
+        stops = self._stops(stop_token_ids)
+        ids = torch.zeros(1, L, dtype=torch.long)
+        am = torch.zeros(1, L, dtype=torch.bool)
+        ids[0, L - len(prompt):] = torch.tensor(prompt, dtype=torch.long)
+        am[0, L - len(prompt):] = True
+        logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
+        self._admit(t, int(torch.argmax(logits, dim=-1)[0]), L, max_new_tokens, stops)
+
+    @torch.no_grad()
+    def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None):
+        """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
+        common padded length."""
+        dec = self.dec
+        assert max_new_tokens >= 1
+        if bool(self.active_flags.any()):
+            raise RuntimeError("a tenant is still generating")
+        stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
+        ids, am = dec.prepare(prompts)
+        L = ids.shape[1]
+        if L > self.Lc:
+            raise ValueError("the padded prompts do not fit the KV cache")
+        first = torch.argmax(dec.prefill(ids, am, self.cache), dim=-1).tolist()
+        for t in range(self.T):
+            self._admit(t, first[t], L, max_new_tokens, stops[t])
+
+    # ------------------------------------------------------------ stepping
+    def _step_once(self):
+        dec = self.dec
+        x = ops.step_begin_ragged(dec.embed, self.tok, self.cache["valid"], self.pos, self.active_flags)
+        logits = dec.forward(self.tok, None, self.cache, None, x=x, ragged=(self.pos, self.active_flags))
+        if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
+            raise RuntimeError("the lm_head output is not laid out for the step kernel (16-byte aligned rows)")
+        ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
+
+    def _state(self):
+        return [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
+
+    def _runner(self):
+        """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
+        stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
+        alone."""
+        dec = self.dec
+        key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr())
+        g = self._graphs.get(key)
+        if g is None:
+            if dec._capture_stream is None:
+                dec._capture_stream = torch.cuda.Stream(device=dec.dev)
+            side = dec._capture_stream
+            snap = [v.clone() for v in self._state()]
+            side.wait_stream(torch.cuda.current_stream(dec.dev))
+            with torch.cuda.stream(side):
+                self._step_once()
+            torch.cuda.current_stream(dec.dev).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                self._step_once()
+            torch.cuda.synchronize(dec.dev)
+            for v, s_ in zip(self._state(), snap):
+                v.copy_(s_)
+            self._graphs[key] = g
+        return g.replay
+
+    @torch.no_grad()
+    def step(self, k=1, use_graph=True):
+        """k ragged steps: every active tenant produces one token per step, at its own position"""
+        if k <= 0:
+            return
+        if not (self.dec.fast_glue and self.dec.step_kernels) or self.dec.prefetch_o:
+            raise RuntimeError("fast_glue / step_kernels / prefetch_o were switched after the session was made")
+        runner = self._runner() if use_graph else self._step_once
+        for _ in range(k):
+            runner()
+
+    def run(self, check_every=1, use_graph=True):
+        """step until no tenant is active; the host polls the activity flags every check_every steps"""
+        while bool(self.active_flags.any()):
+            self.step(check_every, use_graph=use_graph)
+
+    def active(self):
+        """the activity flags on the host: a list of T bools"""
+        return self.active_flags.tolist()
+
+    def result(self, t):
+        """(tokens, reason): tenant t's new tokens so far as a 1-D CPU tensor, and why it stopped (0 while it is active)"""
+        n = min(int(self.n[t]), self.out.shape[1])
+        return self.out[t, :n].cpu(), int(self.done[t])

@@ -90,6 +90,28 @@ def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads)
     return out
 
 
+def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, heads, kv_heads):
+    """decode_attention with one position per tenant: pos int64 [T], active bool [T] on the device.  Tenant t attends over its valid keys
+    0 .. pos[t] and appends at pos[t]; a tenant that is inactive or whose position lies outside the cache gets a zero output row and its cache
+    and valid rows stay as they are."""
+    require_gpu(qkv, cos, sin, kcache, vcache, valid, pos, active)
+    T = qkv.shape[0]
+    hd = kcache.shape[3]
+    assert qkv.shape[1] == 1 and qkv.shape[2] == (heads + 2 * kv_heads) * hd and qkv.stride(2) == 1
+    assert kcache.is_contiguous() and vcache.is_contiguous() and valid.is_contiguous() and valid.dtype == torch.bool
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == qkv.dtype and pos.dtype == torch.int64
+    assert pos.numel() == T and pos.is_contiguous() and active.dtype == torch.bool and active.numel() == T and active.is_contiguous()
+    out = torch.empty((T, 1, heads * hd), device=qkv.device, dtype=qkv.dtype)
+    L = lib()
+    need = L.bd_srv_decode_attention_workspace_bytes(T, heads, kv_heads, hd, kcache.shape[2])
+    ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)          # (the scalar form's persistent scratch, same contract)
+    with torch.cuda.device(qkv.device):
+        check(L.bd_srv_decode_attention_ragged(ptr(qkv), ptr(cos), ptr(sin), ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(active), ptr(out),
+                                               T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
+                                               DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()), "srv_decode_attention_ragged")
+    return out
+
+
 def prefill_attention_supported(q, k, v):
     """the shapes bd_srv_prefill_attention takes: [B, S, heads, 128] views (any batch / sequence strides that are multiples of 8 elements,
     heads contiguous), S a multiple of 64"""
@@ -177,6 +199,41 @@ def step_end(logits, tok, out, step, pos, stop_ids, stopped, ticket):
     with torch.cuda.device(logits.device):
         check(lib().bd_srv_step_end(ptr(logits), logits.stride(0), V, ptr(tok), ptr(out), out.stride(0), out.shape[1], ptr(stop_ids), stop_ids.shape[1],
                                     ptr(stopped), ptr(pos), ptr(step), ptr(ticket), T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_end")
+
+
+def step_begin_ragged(embed, tok, valid, pos, active):
+    """step_begin with per-tenant state: x[t] = embed[t, tok[t]] and valid[t, pos[t]] = True for an active tenant whose position lies in the cache;
+    a zero row and no mark otherwise.  pos [T] long, active [T] bool."""
+    require_gpu(embed, tok, valid, pos, active)
+    shared = embed.dim() == 2
+    V, H = embed.shape[-2], embed.shape[-1]
+    T = tok.shape[0]
+    assert tok.dtype == torch.long and tok.is_contiguous() and tok.numel() == T and pos.dtype == torch.long and pos.numel() == T and pos.is_contiguous()
+    assert valid.dtype == torch.bool and valid.is_contiguous() and valid.shape[0] == T and (shared or embed.shape[0] == T)
+    assert embed.stride(-1) == 1 and H % 8 == 0 and active.dtype == torch.bool and active.numel() == T and active.is_contiguous()
+    x = torch.empty((T, 1, H), device=embed.device, dtype=embed.dtype)
+    with torch.cuda.device(embed.device):
+        check(lib().bd_srv_step_begin_ragged(ptr(embed), 0 if shared else embed.stride(0), embed.stride(-2), ptr(tok), ptr(x), H, ptr(valid),
+                                             valid.shape[1], ptr(pos), ptr(active), T, V, H, stream_ptr()), "srv_step_begin_ragged")
+    return x
+
+
+def step_end_ragged(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len):
+    """Last launch of a ragged step, per ACTIVE tenant: nxt = argmax(logits[t]); tok[t] = nxt; out[t, n[t]] = nxt; n[t] += 1; pos[t] += 1; and the
+    tenant retires (active[t] = False, done[t] = reason) when nxt is one of its stop ids (1), n[t] reached limit[t] (2) or pos[t] reached
+    cache_len (4).  logits [T, V] 16-bit; n / pos / limit [T] long; active [T] bool; done [T] uint8."""
+    require_gpu(logits, tok, out, n, pos, limit, stop_ids, active, done)
+    T, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and tok.dtype == torch.long and tok.is_contiguous() and tok.numel() == T
+    assert out.dtype == torch.long and out.shape[0] == T and out.stride(1) == 1 and stop_ids.dtype == torch.long and stop_ids.is_contiguous()
+    assert stop_ids.shape[0] == T and active.dtype == torch.bool and active.is_contiguous() and active.numel() == T
+    assert done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == T
+    for v in (n, pos, limit):
+        assert v.dtype == torch.long and v.numel() == T and v.is_contiguous()
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_end_ragged(ptr(logits), logits.stride(0), V, ptr(tok), ptr(out), out.stride(0), out.shape[1], ptr(stop_ids),
+                                           stop_ids.shape[1], ptr(pos), ptr(n), ptr(limit), ptr(active), ptr(done), int(cache_len), T,
+                                           DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_end_ragged")
 
 
 def rope_kv_append_(qkv, cos, sin, kcache, vcache, heads, kvh, pos0=0):

@@ -275,6 +275,20 @@ int bd_srv_step_begin(const void* embed, int64_t sEt, int64_t sEv, const int64_t
                       const int64_t* pos, int T, int V, int H, void* stream);
 int bd_srv_step_end(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
                     const int64_t* stop_ids, int ns, void* stopped, int64_t* pos, int64_t* step, void* ticket, int T, int dtype, void* stream);
+/* bd_srv_step_begin_ragged / bd_srv_step_end_ragged: the same two ends with PER-TENANT state, so that a tenant is admitted while the others are
+ * mid-generation and retires at its own stop token (serving_loop.TenantSession).  pos / n / limit are int64 [T], active / done bytes [T].
+ * step_begin_ragged: tenant t is LIVE when active[t] != 0 and 0 <= pos[t] < Lc.  Live: X[t] = embed[t][clamp(tok[t], 0, V - 1)] and
+ *   valid[t, pos[t]] = 1.  Not live: X[t] = 0 (a zero row stays finite through RMSNorm and every Linear) and valid is not touched.  The range
+ *   guard is part of the contract: pos advances on the device without the host seeing it.
+ * step_end_ragged: one block per tenant, no ticket, no shared counter.  active[t] == 0: nothing of tenant t is read or written.  Otherwise, in
+ *   this order: nxt = argmax(logits[t, :V]) (torch.argmax's order, as step_end); tok[t] = nxt; out[t, n[t]] = nxt when 0 <= n[t] < out_cap (out
+ *   [T, >= out_cap] int64, row stride s_out); n[t] += 1; pos[t] += 1; reason = (nxt in stop_ids[t, :ns] ? 1 : 0) | (n[t] >= limit[t] ? 2 : 0) |
+ *   (pos[t] >= Lc ? 4 : 0); when reason != 0: active[t] = 0 and done[t] = reason.  done is written only then.  V % 8 == 0, sl % 8 == 0.  Exact. */
+int bd_srv_step_begin_ragged(const void* embed, int64_t sEt, int64_t sEv, const int64_t* tok, void* X, int64_t sx, void* valid, int Lc,
+                             const int64_t* pos, const void* active, int T, int V, int H, void* stream);
+int bd_srv_step_end_ragged(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
+                           const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done, int Lc, int T,
+                           int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
@@ -283,6 +297,16 @@ int bd_srv_cache_warm(const void* p0, int64_t bytes0, const void* p1, int64_t by
 int bd_srv_decode_attention(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, void* valid,
                             const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
                             int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
+/* bd_srv_decode_attention_ragged: bd_srv_decode_attention with one position per tenant.  pos int64 [T], active bytes [T] (both on the device);
+ *   everything else as there, including the validation, the workspace (bd_srv_decode_attention_workspace_bytes, same ticket contract), the
+ *   split rule and the ring depth: at equal positions it is the same launch geometry and the same bits.  Tenant t's key range 0..pos[t], its
+ *   split bounds, its RoPE table row, its cache append at pos[t] and its valid[t, pos[t]] mark all follow its own position.  A tenant with
+ *   active[t] == 0, pos[t] < 0 or pos[t] >= Lc stays out of the launch: nothing is appended or marked, its H*128 outputs are written as zeros,
+ *   and its blocks leave before any partial store or ticket increment (every split of a (tenant, kv head) pair takes the same decision, so
+ *   the tickets are zero at exit).  The range guard is part of the contract: pos is device data that advances without the host seeing it. */
+int bd_srv_decode_attention_ragged(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, void* valid,
+                                   const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                   int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
 /* bd_srv_prefill_attention: attention of a whole prompt (the prefill call of the serving loop, demo/demo_backend.py:262-275 -> the HF
  *   decoder layer's attention with the left-padded attention_mask; what F.scaled_dot_product_attention computes there), flash-style:
  *   O[b, s, h] = softmax_k(Q[b, s, h] . K[b, k, h / (H/KVH)] * scale) . V[b, k, h / (H/KVH)] over the keys kv_start[b] <= k (<= s when
