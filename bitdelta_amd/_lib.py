@@ -16,6 +16,8 @@ BD_F16, BD_BF16, BD_F32 = 0, 1, 2
 DTYPE_CODE = {torch.float16: BD_F16, torch.bfloat16: BD_BF16, torch.float32: BD_F32}
 WORD_DTYPE = {8: torch.uint8, 16: torch.int16, 32: torch.int32, 64: torch.int64}
 
+BD_DECODE_PLAN_INTS = 21          # include/bitdelta_hip_test.h: the record of bd_last_decode_plan
+
 _i64, _vp, _ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
 # name -> (restype, argtypes); must list every symbol declared in include/bitdelta_hip.h (tests check this)
@@ -73,6 +75,8 @@ SIGNATURES = {
     "bd_set_decode_small_lut": (_ci, [_ci]),
     "bd_set_stream_tuning": (_ci, [_ci]),
     "bd_last_decode_form": (_ci, []),
+    "bd_last_decode_plan": (_ci, [ctypes.POINTER(ctypes.c_int32), _ci]),
+    "bd_set_decode_dry_run": (_ci, [_ci]),
     "bd_last_attention_form": (_ci, []),
     "bd_set_decode_generic_loop": (_ci, [_ci]),
     "bd_set_decode_engine": (_ci, [_ci]),

@@ -1,4 +1,6 @@
 // C ABI of libbitdelta_hip.so (see include/bitdelta_hip.h): argument checking + kernel dispatch.
+// The decode Linear's streaming kernel is dispatched in two steps: stream_plan() decides (plain host code: form, depth, cache policy, grid, LDS)
+// and launch_stream() lifts the plan to the one instantiation of the shipped set, stream_shipped(); bd_last_decode_plan reports the plan.
 // No torch types.  State: the test / tuning overrides (bd_set_*) are THREAD-LOCAL, so a thread that forces a kernel family does not
 // change what other threads launch; the per-DEVICE caches (CU count, "max dynamic LDS already raised for this kernel") are keyed
 // by the current device id -- the reference's demo runs one process over several GPUs (demo/demo_backend.py:23-25).
@@ -24,6 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
+#include <tuple>
 
 using namespace bd;
 
@@ -58,7 +61,6 @@ static thread_local int g_ring_tune = -1;             // variant 700 knobs, -1 =
                                                       // ring even when a resident copy fits, bit 2 = ONE loader wave (default two), bits 8..13 = cap on
                                                       // the ring slots (0 = none)
 static thread_local int t_last_variant = -1;
-static thread_local int t_last_decode_form = 0;    // 1 = the last streaming decode launch took the fine-grid form
 static thread_local int t_last_attention_form = 0; // decode_attn_kernel instantiation of the last launch: nsplit | DEPTH << 8 | MAXS << 16 | G << 24
 
 extern "C" int bd_version(void) { return 1; }
@@ -71,7 +73,6 @@ extern "C" int bd_set_decode_wave_spec(int on) { g_gemv_wave_spec = on ? 1 : 0; 
 extern "C" int bd_set_launch_chunking(int on) { g_launch_chunking = on ? 1 : 0; return BD_OK; }
 extern "C" int bd_set_decode_generic_loop(int on) { g_col16_no_per4 = on ? 1 : 0; return BD_OK; }
 extern "C" int bd_set_stream_tuning(int flags) { g_stream_tune = flags; return BD_OK; }
-extern "C" int bd_last_decode_form(void) { return t_last_decode_form; }
 extern "C" int bd_last_attention_form(void) { return t_last_attention_form; }
 extern "C" int bd_set_decode_engine(int engine) { g_decode_engine = engine < 0 ? -1 : (engine ? 1 : 0); return BD_OK; }
 extern "C" int bd_set_ring_tuning(int flags) { g_ring_tune = flags; return BD_OK; }
@@ -228,7 +229,12 @@ inline bool gemv_ok(const Problem& q) {
     return ok;
 }
 
-inline int gemv_rmax(int R) { return R <= 1 ? 1 : R <= 2 ? 2 : R <= 3 ? 3 : R <= 4 ? 4 : R <= 6 ? 6 : R <= 8 ? 8 : R <= 12 ? 12 : 16; }
+// f(std::integral_constant<int, V>) for the first V of the ascending list with n <= V (the last V beyond it): a count to its bucket's template argument
+template <int... Vs, class F>
+void for_bucket(int n, F&& f) {
+    constexpr int last = std::max({Vs...});
+    (void)(((n <= Vs || Vs == last) && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
 
 inline void gemv_split(const Problem& q, int& KS, int& kslice) {
     const int tiles_n = (q.N + 63) / 64;
@@ -316,36 +322,34 @@ int launch_gemv_col16(const Problem& q, const GemvParams& gp) {
     return launch_gemv_col16_per<DT, NM, 1>(q, gp);
 }
 
-template <int DT>
-int launch_gemv_col16_chunk(const Problem& q) {
+// what every decode kernel reads of the problem: one k slice, no split-k scratch (the split-k kernels set KS / kslice / ws / tickets themselves)
+inline GemvParams gemv_params(const Problem& q) {
     GemvParams gp;
     gp.X = (const unsigned short*)q.A;
     gp.P = (const uint32_t*)q.P;
     gp.W = (const unsigned short*)q.W;
     gp.alpha = q.alpha;
     gp.C = q.C;
+    gp.ws = nullptr; gp.tickets = nullptr;
     gp.B = q.B; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.R = q.B * q.M;
     gp.sXb = q.sAb; gp.sPb = q.sPb; gp.sCb = q.sCb;
     gp.sXm = (int)q.sAm; gp.sCm = (int)q.sCm; gp.ldw = (int)q.ldw; gp.sAlb = (int)q.sAlb; gp.gsz = q.N / q.G;
+    gp.KS = 1; gp.kslice = q.K;
+    gp.round_mode = q.round_mode; gp.accumulate = q.accumulate; gp.out_f32 = (q.out_dtype == BD_F32);
+    return gp;
+}
+
+template <int DT>
+int launch_gemv_col16_chunk(const Problem& q) {
+    GemvParams gp = gemv_params(q);
     const int forced = (g_forced_variant > 500 && g_forced_variant <= 564) ? g_forced_variant - 500 : 0;
     col16_split(gp.R, q.K, forced, gp.KS, gp.kslice);
-    gp.round_mode = q.round_mode; gp.accumulate = q.accumulate; gp.out_f32 = (q.out_dtype == BD_F32);
-    gp.tickets = nullptr;
-    gp.ws = nullptr;
     if (gp.KS > 1) {
         const int64_t need = GEMV_TICKET_BYTES + (int64_t)gp.KS * gp.R * q.N * 4;
         if (!q.ws || q.ws_bytes < need) return BD_E_WORKSPACE;
         gp.ws = (float*)((char*)q.ws + GEMV_TICKET_BYTES);
     }
-    const int nm = q.sPb == 0 ? 1 : q.B;
-    if (nm <= 1) launch_gemv_col16<DT, 1>(q, gp);
-    else if (nm <= 2) launch_gemv_col16<DT, 2>(q, gp);
-    else if (nm <= 3) launch_gemv_col16<DT, 3>(q, gp);
-    else if (nm <= 4) launch_gemv_col16<DT, 4>(q, gp);
-    else if (nm <= 6) launch_gemv_col16<DT, 6>(q, gp);
-    else if (nm <= 8) launch_gemv_col16<DT, 8>(q, gp);
-    else if (nm <= 12) launch_gemv_col16<DT, 12>(q, gp);
-    else launch_gemv_col16<DT, 16>(q, gp);
+    for_bucket<1, 2, 3, 4, 6, 8, 12, 16>(q.sPb == 0 ? 1 : q.B, [&](auto NM) { launch_gemv_col16<DT, NM>(q, gp); });
     if (gp.KS > 1) {
         dim3 g2((unsigned)((q.N + 255) / 256), (unsigned)gp.R);
         hipLaunchKernelGGL((gemv_reduce_kernel<DT>), g2, dim3(256), 0, q.st, gp);
@@ -371,39 +375,142 @@ inline bool stream_ok(const Problem& q, int rows, int nmask) {
 }
 
 constexpr int STREAM_LDS_MAX = 160 * 1024;        // LDS of a gfx950 CU: the fused-norm kernels add R activation rows to STREAM_LDS_BYTES
-template <int DT, int NM, bool HASW, int NS, int NW = 8, int WNAT = 0, int AUX = 2, int PK = 0, int XL = 0, int EPI = 0, int WT = 0, int FG = 0>
-int launch_stream_inst(const StreamParams& sp, dim3 grid, hipStream_t st) {
+
+// ---- which gemv_stream_kernel serves a launch.  The DECISION (stream_plan, below: plain host code, no HIP call) and the LAUNCH
+// (launch_stream) are separate: every form of this Linear produces the same bits by design, so a launch that took the wrong prefetch depth,
+// cache policy or grid would only be slower and no output test could see it -- the plan is what the host tests pin (bd_last_decode_plan,
+// tests/golden/stream_dispatch.txt), and the set of compiled kernels is stream_shipped() and nothing else (tests/golden/stream_kernel_forms.txt).
+// The kernel's twelve template parameters as run-time values (-1 = not decided yet), in the order they are lifted to template arguments -- which is
+// the kernels' order in the code object: NM early keeps one step's forms neighbours (0.9 % of the step, profiles/decode_dispatch_refactor.txt)
+struct StreamForm {
+    int DT = -1, PK = -1, WT = -1, NM = -1, XL = -1, FG = -1, HASW = -1, WNAT = -1, AUX = -1, EPI = -1, NS = -1, NW = -1;
+};
+template <int... Vs> struct Vals {};
+// the values each parameter can take, in StreamForm's order (FG 2, AUX 6, NS 12 and NW 8: harness builds, -DBD_AB_VARIANTS)
+using StreamAxes = std::tuple<Vals<DT_F16, DT_BF16>, Vals<0, 1>, Vals<0, 1, 2, 3>, Vals<0, 1, 2, 3, 4, 6, 8, 12, 16>, Vals<0, 1, 2, 3>, Vals<0, 1, 2>,
+                              Vals<0, 1>, Vals<0, 1>, Vals<0, 2, 6>, Vals<0, 1>, Vals<2, 3, 4, 6, 8, 12>, Vals<4, 8>>;
+constexpr int STREAM_FORM_FIELDS = std::tuple_size_v<StreamAxes>;
+#ifdef BD_AB_VARIANTS
+constexpr bool STREAM_AB = true;
+#else
+constexpr bool STREAM_AB = false;
+#endif
+
+// NS = stages of loads in flight per wave: a function of the sign layout, the activation source, the mask count and the weight format, nothing else.
+constexpr int stream_depth(int PK, int XL, int NM, int WT) {
+    // reference / tile-major sign layouts (and bd_tenant_linear, NM = 0; NS 6 / 4 measured equal or slower there): bounded by the 256-VGPR
+    // budget of a 2-waves-per-SIMD block (hipcc spills beyond)
+    if (!PK) return NM <= 1 ? 8 : NM == 2 ? 6 : 4;
+    // Prefetch depth of the int8 forms: a stage carries HALF the weight bytes, and what saturates HBM is bytes in flight per wave, not stages.
+    // With one or two tenants the int8 launches ran latency-bound at the 16-bit depths and twice the stages put the same bytes in flight
+    // (1 tenant, gate|up 31.3 -> 26.8 us, step 2.55 -> 2.31 ms); from 4 tenants on the sign work bounds the stage, the deeper queue only adds
+    // latency (6 tenants: q|k|v 17.4 -> 18.8 us, o 13.0 -> 14.1) and the norm-prologue form spills: same depth as 16 bits
+    // (rocprofv3 kernel traces, profiles/w8_decode_step.txt).
+    // The 4-bit forms follow the same rule with a QUARTER of the weight bytes per stage: one or two tenants run four times the 16-bit depth where
+    // the activation rows are resident (a stage is 3 loads: nibbles, group parameters, signs -- 8 stages keep 21 loads in flight, far inside the
+    // 6-bit vmcnt) and twice where every stage also loads its four activation fragments (7 loads per stage: 4 x 3 stages would need 77 counts);
+    // from 4 tenants on the 16-bit depth, for int8's measured reason.
+    const bool few = WT >= 2 && NM <= 2;
+    // Resident rows, hand-off consumer, norm prologue: TWO stages.  Same-process A/Bs of the whole step late in round 4
+    // (profiles/r04_decode_step_ab.txt): 8 -> 6 -> 4 -> 2 stages each made the step faster (1 tenant: 3.57 -> 3.32 ms over the whole sequence
+    // of changes; 6 tenants: -0.3 % for the resident-row form alone; gate|up with its norm at 2 instead of 4 stages: -1 % on the whole step) --
+    // the memory system is saturated by far fewer loads in flight than the register file can hold, and beyond that point a deeper queue only
+    // adds latency (returns are in issue order).  (The parity of NS selects the activation fragment set, so 2 is the minimum.)
+    if (XL) return few ? (WT == 3 ? 8 : 4) : 2;
+    // plain / SwiGLU-only forms: 1 tenant 3 stages (8 until late in round 4: -6 % on the single-delta step over 8 -> 6 -> 4 -> 3), 2 tenants 4
+    // (6: +3 %), 4 and more 4 (3 measured +0.6 % at 6 tenants; NS 6 with nt weight loads measured 5-14 % slower: tools/ab_decode_depth.py)
+    return (NM == 1 ? 3 : 4) * (few ? 2 : 1);
+}
+
+// The instantiations the library ships.  Fields are decided in StreamForm's order: a rule on a field reads only the fields before it (a later one
+// is still -1), and a form whose decided fields already break a rule is out, whatever follows (the lifter below stops there).
+// Per dtype 296: reference layout 12 (6 mask counts, fused / delta only) + 3 bd_tenant_linear; packed with row-major W 29 (5 delta only, 7 plain, 7 SwiGLU,
+// 10 norm); per tile-major format 84 = 28 per-stage (7 paddings x SwiGLU x nt) + 20 norm (5 x 2 x 2) + 36 resident / hand-off (2 x 2 x (5 + 4 fine grid)).
+constexpr bool stream_shipped(const StreamForm& f) {
+    const bool nm8 = f.NM == 1 || f.NM == 2 || f.NM == 4 || f.NM == 6 || f.NM == 8;                  // packed layout: tenants padded to ...
+    const bool ref = !f.PK && !f.WT && !f.XL && !f.FG;
+    // harness builds add the bd_set_stream_tuning bits 0-3 matrix (fp16, fused, 0 / 1 / 6 masks: W order x nt policy x 8-wave blocks x deeper
+    // prefetch) and the two-pass resident rows (FG = 2: 4 / 6 tenants, 2 or 4 stages)
+    const bool ab = STREAM_AB && ref && f.DT == DT_F16 && f.HASW != 0 && (f.NM == 0 || f.NM == 1 || f.NM == 6);
+    if (f.WT > 0 && !f.PK) return false;                                   // tile-major W: packed signs only
+    if (f.NM >= 0 && !(f.PK ? (nm8 || f.NM == 12 || f.NM == 16) : (f.NM <= 4 || f.NM == 6 || f.NM == 8))) return false;   // (0 = bd_tenant_linear)
+    // norm prologue: packed; resident rows / hand-off: tile-major W; 9 .. 16 tenants: plain / SwiGLU only; fine grid: resident rows, <= 6 tenants
+    if (f.XL > 0 && !(f.PK && (f.WT || f.XL == 1) && nm8)) return false;
+    if (f.FG > 0 && !(f.XL >= 2 && ((f.FG == 1 && f.NM <= 6) || (STREAM_AB && f.FG == 2 && f.WT == 1 && f.XL == 2 && (f.NM == 4 || f.NM == 6))))) return false;
+    if (f.HASW == 0 && !(f.NM >= 1 && f.NM <= 8 && !f.WT && !f.XL)) return false;           // delta only: no fused form
+    if (f.WNAT >= 0 && f.WNAT != f.PK && !(ref && f.NM == 0 && f.HASW) && !ab) return false;           // natural-order W off the packed layout
+    if (f.AUX > 0 && !(f.AUX == 2 && (f.PK ? f.WT != 0 : (f.NM == 0 && f.WNAT == 1))) && !(ab && f.AUX == 6)) return false;   // nt loads
+    if (f.AUX == 0 && f.XL >= 2) return false;                            // (the resident-row forms have no default-policy twin)
+    if (f.EPI > 0 && !(f.PK && f.HASW && f.FG != 2)) return false;        // SwiGLU: packed, fused
+    const int depth = stream_depth(f.PK, f.XL, f.NM, f.WT);
+    const bool abm = ab && f.AUX != 2;                     // (the matrix: AUX 0 / 6)
+    if (f.NS >= 0 && f.NS != depth && !(abm && (2 * f.NS == depth || 4 * f.NS == 3 * depth || 2 * f.NS == 3 * depth)) &&
+        !(f.FG == 2 && f.NS == 4)) return false;
+    if (f.NW >= 0 && f.NW != (abm && f.NS < depth ? 8 : 4)) return false;            // (8-wave blocks run half the stages per wave)
+    return true;
+}
+
+// What stream_plan decides about one launch; bd_last_decode_plan reports it field by field.
+struct StreamPlan {
+    int rc = BD_OK;                    // != BD_OK: the launch is refused
+    StreamForm f;
+    unsigned grid = 0, grid_y = 1;     // (grid_y: bd_tenant_linear's tenants)
+    int block = 0, lds = 0;            // threads per block, dynamic LDS bytes
+    int cpb = 0; uint32_t xs_off = 0, xrow = 0;      // StreamParams::cpb / xs_off / xrow
+    int form = 0;                      // bd_last_decode_form: 0 = one block per CU, 1 = fine grid, 2 = two-pass resident rows (harness builds)
+#ifdef BD_AB_VARIANTS
+    bool ring = false;                 // handed over to the loader / consumer kernel (variant 700)
+#endif
+};
+static thread_local StreamPlan t_last_plan;         // of this thread's last streaming decode launch or dry run
+static thread_local int g_decode_dry_run = 0;       // bd_set_decode_dry_run: plan and record, never touch the device
+
+// block size and dynamic LDS of the planned form; refuses what does not fit
+inline void stream_plan_lds(StreamPlan& pl, int R) {
+    const StreamForm& f = pl.f;
+    const int base = f.FG ? STREAM_FG_XS_OFF : STREAM_LDS_BYTES;
+    pl.block = 64 * f.NW;
+    pl.lds = f.XL ? std::max((int)(pl.xs_off + (uint32_t)R * pl.xrow), base) : base;
+    if (pl.lds > (f.FG == 1 ? STREAM_FG_LDS_MAX : STREAM_LDS_MAX)) pl.rc = BD_E_BAD_SHAPE;
+}
+
+template <int DT, int NM, bool HASW, int NS, int NW, int WNAT, int AUX, int PK, int XL, int EPI, int WT, int FG>
+int launch_stream_inst(const StreamPlan& pl, const StreamParams& sp, hipStream_t st) {
+    if (g_decode_dry_run) return BD_OK;
     auto kern = gemv_stream_kernel<DT, NM, HASW, NS, NW, WNAT, AUX, PK, XL, EPI, WT, FG>;
     static std::atomic<uint64_t> lds_done{0};
-    constexpr int base = FG ? STREAM_FG_XS_OFF : STREAM_LDS_BYTES;
-    const int lds = XL ? std::max((int)(sp.xs_off + (uint32_t)sp.g.R * sp.xrow), base) : base;
-    if (lds > (FG == 1 ? STREAM_FG_LDS_MAX : STREAM_LDS_MAX)) return BD_E_BAD_SHAPE;
     if (!ensure_dyn_lds((const void*)kern, FG == 1 ? STREAM_FG_LDS_MAX : XL ? STREAM_LDS_MAX : STREAM_LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, sp);
+    hipLaunchKernelGGL(kern, dim3(pl.grid, pl.grid_y), dim3(pl.block), pl.lds, st, sp);
     return BD_OK;
 }
 
-// Shipped configuration (profiles/r02_decode_stream_ab.txt): 4-wave blocks (one wave per SIMD, the whole register file: NS4 stages
-// of loads in flight per wave), word-row order for W, default cache policy.  Harness builds (-DBD_AB_VARIANTS) add the A/B matrix
-// selected by bd_set_stream_tuning: bit 0 natural-order W, bit 1 nt cache policy, bit 2 8-wave blocks (two waves per SIMD), bit 3 the
-// deeper of two prefetch depths.
-template <int DT, int NM, bool HASW, int NS4>
-int launch_stream_tuned(const StreamParams& sp, dim3 grid, hipStream_t st) {
-#ifdef BD_AB_VARIANTS
-    if constexpr (DT == DT_F16 && HASW && (NM == 0 || NM == 1 || NM == 6)) {
-        constexpr int A8 = NM == 6 ? 2 : 4, B8 = NM == 6 ? 3 : 6;          // 8-wave blocks: base / deeper
-        constexpr int A4 = NM == 6 ? 4 : 8, B4 = NM == 6 ? 6 : 12;         // 4-wave blocks
-        switch (g_stream_tune & 15) {
-#define BD_T(code, NS, NW, WN, AX) case code: return launch_stream_inst<DT, NM, HASW, NS, NW, WN, AX>(sp, grid, st)
-            BD_T(0, A4, 4, 0, 0); BD_T(1, A4, 4, 1, 0); BD_T(2, A4, 4, 0, 6); BD_T(3, A4, 4, 1, 6);
-            BD_T(4, A8, 8, 0, 0); BD_T(5, A8, 8, 1, 0); BD_T(6, A8, 8, 0, 6); BD_T(7, A8, 8, 1, 6);
-            BD_T(8, B4, 4, 0, 0); BD_T(9, B4, 4, 1, 0); BD_T(10, B4, 4, 0, 6); BD_T(11, B4, 4, 1, 6);
-            BD_T(12, B8, 8, 0, 0); BD_T(13, B8, 8, 1, 0); BD_T(14, B8, 8, 0, 6); BD_T(15, B8, 8, 1, 6);
-#undef BD_T
-        }
+// Lifts the run-time values of a form to template arguments, one field per level: a fold over the field's value list compares and recurses.
+// A prefix that stream_shipped() rules out ends there, so exactly the shipped forms are instantiated; anything else answers BD_E_BAD_SHAPE.
+template <int... Done>
+struct StreamLift {
+    static int run(const int* want, const StreamPlan& pl, const StreamParams& sp, hipStream_t st) {
+        constexpr StreamForm f{Done...};
+        if constexpr (!stream_shipped(f)) return BD_E_BAD_SHAPE;
+        else if constexpr (sizeof...(Done) == STREAM_FORM_FIELDS)
+            return launch_stream_inst<f.DT, f.NM, f.HASW != 0, f.NS, f.NW, f.WNAT, f.AUX, f.PK, f.XL, f.EPI, f.WT, f.FG>(pl, sp, st);
+        else return next(std::tuple_element_t<sizeof...(Done), StreamAxes>{}, want, pl, sp, st);
     }
-#endif
-    return launch_stream_inst<DT, NM, HASW, NS4, 4, 0, 0>(sp, grid, st);
+    template <int... Vs>
+    static int next(Vals<Vs...>, const int* want, const StreamPlan& pl, const StreamParams& sp, hipStream_t st) {
+        int rc = BD_E_BAD_SHAPE;      // (a value outside the list)
+        (void)((want[sizeof...(Done)] == Vs && ((rc = StreamLift<Done..., Vs>::run(want, pl, sp, st)), true)) || ...);
+        return rc;
+    }
+};
+
+// The one launcher of gemv_stream_kernel: records the plan, launches it unless this is a dry run, answers the launch status.
+inline int launch_stream(StreamPlan pl, const StreamParams& sp, hipStream_t st) {
+    const StreamForm& f = pl.f;
+    const int want[STREAM_FORM_FIELDS] = {f.DT, f.PK, f.WT, f.NM, f.XL, f.FG, f.HASW, f.WNAT, f.AUX, f.EPI, f.NS, f.NW};
+    if (pl.rc == BD_OK) pl.rc = StreamLift<>::run(want, pl, sp, st);
+    t_last_plan = pl;
+    if (pl.rc != BD_OK || g_decode_dry_run) return pl.rc;
+    return launch_status();
 }
 
 #ifdef BD_AB_VARIANTS
@@ -434,60 +541,142 @@ int launch_ring_inst2(const RingParams& rp, unsigned grid, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (4 + rp.nl)), lds, st, rp);
     return BD_OK;
 }
-template <int DT, int NM>
-int launch_ring_inst(const RingParams& rp, unsigned grid, hipStream_t st) {
-    return rp.nt ? launch_ring_inst2<DT, NM, 1>(rp, grid, st) : launch_ring_inst2<DT, NM, 0>(rp, grid, st);
+template <int NM>
+int launch_ring_inst(int dtype, const RingParams& rp, unsigned grid, hipStream_t st) {
+    if (dtype == BD_BF16) return rp.nt ? launch_ring_inst2<DT_BF16, NM, 1>(rp, grid, st) : launch_ring_inst2<DT_BF16, NM, 0>(rp, grid, st);
+    return rp.nt ? launch_ring_inst2<DT_F16, NM, 1>(rp, grid, st) : launch_ring_inst2<DT_F16, NM, 0>(rp, grid, st);
 }
 
 #endif
 
-// W8 = 1: the int8 tile-major base weight of bd_binary_linear_decode_w8 (q.w_tiled == 2): the same dispatch rules, the WT = 2 instantiations
-// W8 = 2: the 4-bit GPTQ tile-major base weight of bd_binary_linear_decode_q4 (q.w_tiled == 3): the same rules again, the WT = 3 instantiations
-template <int DT, int W8 = 0>
+// Harness builds (STREAM_AB): bd_set_stream_tuning bits 0-3, the A/B matrix of the reference-layout forms (fp16, fused, 0 / 1 / 6 masks): bit 0
+// natural-order W, bit 1 nt cache policy, bit 2 8-wave blocks (two waves per SIMD, half the stages each), bit 3 the deeper prefetch (x 1.5)
+inline void stream_plan_tuned(StreamForm& f) {
+    const int t = g_stream_tune & 15;
+    if (f.DT != DT_F16 || !f.HASW || !(f.NM == 0 || f.NM == 1 || f.NM == 6)) return;
+    f.WNAT = t & 1; f.AUX = (t & 2) ? 6 : 0; f.NW = (t & 4) ? 8 : 4;
+    f.NS = f.NS * ((t & 8) ? 3 : 2) / ((t & 4) ? 4 : 2);
+}
+
+// The decision.  Reads the problem, the CU count and this thread's tuning state (forced variant, bd_set_stream_tuning); makes no HIP call.
+// q.w_tiled is the weight format: 0 row-major, 1 tile-major, 2 = the int8 tile-major copy of bd_binary_linear_decode_w8, 3 = the 4-bit GPTQ copy
+// of bd_binary_linear_decode_q4 -- the same rules for all of them, the kernel's WT.
+StreamPlan stream_plan(const Problem& q, int cus) {
+    StreamPlan pl;
+    StreamForm& f = pl.f;
+    f.DT = q.dtype == BD_BF16 ? DT_BF16 : DT_F16;
+    f.PK = q.mask_tiled == 2; f.WT = q.w_tiled; f.XL = 0; f.FG = 0;
+    f.HASW = q.W != nullptr; f.WNAT = f.PK; f.AUX = 0; f.EPI = f.PK && q.epilogue == 1; f.NW = 4;
+    const int nmask = q.sPb == 0 ? 1 : q.B;
+    // columns per block: the whole chip streams one launch, so every CU gets ~N / CUs columns (rounded up to whole sign-word
+    // quads); a few more blocks than CUs would serialise a second, nearly empty round
+    int cpb = (q.N + cus - 1) / cus;
+    cpb = (cpb + 3) & ~3;
+    if (cpb < 4) cpb = 4;
+    if (g_forced_variant > 600 && g_forced_variant <= 664) cpb = 4 * (g_forced_variant - 600);     // test hook: 600 + cpb/4
+    if (q.epilogue == 1 || q.ssq_out) cpb = (cpb + 15) & ~15;      // whole [8 gate | 8 up] tiles / whole hand-off tiles per block
+    pl.cpb = cpb;
+    pl.grid = (unsigned)((q.N + cpb - 1) / cpb);
+    pl.xs_off = (uint32_t)STREAM_XS_OFF; pl.xrow = (uint32_t)q.K * 2u + 16u;
+    if (!f.PK) {
+        // reference / tile-major sign layouts: accumulator sets = distinct masks (extra sets of a bucket repeat the last mask)
+        // Shipped configuration (profiles/r02_decode_stream_ab.txt): 4-wave blocks (one wave per SIMD, the whole register file: NS stages
+        // of loads in flight per wave), word-row order for W, default cache policy.
+        f.NM = nmask <= 4 ? (nmask < 1 ? 1 : nmask) : nmask <= 6 ? 6 : 8;
+        f.NS = stream_depth(f.PK, f.XL, f.NM, f.WT);
+        if (STREAM_AB) stream_plan_tuned(f);
+        stream_plan_lds(pl, q.B * q.M);
+        return pl;
+    }
+    // packed layout: all tenants of the call in one chunk, interleaved
+    // kernel kinds: plain | RMSNorm prologue (XL) | XL + SwiGLU epilogue | SwiGLU epilogue only; each with row-major or tile-major W (WT)
+    f.NM = q.t_pad;
+#ifdef BD_AB_VARIANTS
+    if (ring_wanted() && q.w_tiled <= 1) {      // loader / consumer kernel (variant 700); launches outside its envelope stay on the streaming kernel
+        RingParams rp{};
+        if (ring_plan(q, rp)) { pl.ring = true; return pl; }
+        if (g_forced_variant == 700) { pl.rc = BD_E_BAD_SHAPE; return pl; }
+    }
+#else
+    if (g_forced_variant == 700) { pl.rc = BD_E_BAD_SHAPE; return pl; }      // harness-only kernel (round 4 A/B loser): never silently replaced
+#endif
+    // tile-major W: optional nt policy on the weight loads (STREAM_WT_NT_DEFAULT, or bd_set_stream_tuning bit 4 = on / bit 5 = off)
+    const bool wnt = (g_stream_tune & 16) ? true : (g_stream_tune & 32) ? false : (STREAM_WT_NT_DEFAULT != 0);
+    // ... and optionally the activation rows resident in LDS with a deeper weight prefetch (XL = 2; bd_set_stream_tuning bit 6 = on,
+    // bit 7 = off): plain and SwiGLU launches with M = 1 and R * K <= 32768
+    // (any K: tile-major W already needs K % 128 == 0; the norm prologue keeps its power-of-two rule, this form does not need it)
+    // Every wave must own at least one 128-k iteration: a wave with an empty k range still walks one padded stage per tile, whose
+    // zero sign words expand to -1 fragments -- harmless against the zero activation fragments of the per-stage form, NOT against
+    // fragments read from the resident rows (K = 1152: 9 iterations over 4 waves leave the last wave empty).
+    const int nit_x = (q.K + 127) / 128;
+    const bool xres_ok = q.w_tiled && (!q.norm_w || q.ssq_in) && q.M == 1 && q.t_pad <= 8 && q.K >= 1024 && 3 * ((nit_x + 3) / 4) < nit_x &&
+                         (int64_t)q.B * q.K <= 16 * 2048 &&
+                         (int64_t)STREAM_XS_OFF + (int64_t)q.B * (2 * (int64_t)q.K + 16) <= STREAM_LDS_MAX;
+    // Fine grid (FG, round 6; gemv_stream_kernel): a resident-row launch whose 16-column tiles number between one and two per CU --
+    // Mistral's fused q|k|v: 384 tiles -- runs as ONE round of single-tile blocks, two per CU (<= 80 KB of LDS with the nibble sign table,
+    // <= 256 VGPRs), instead of 256 blocks that walk 1.5 tiles each.  bd_set_stream_tuning: 256 = never, 512 = every eligible launch
+    // with at most two tiles per CU (one tile per CU included: the o projection).
+    const int fg_tiles = q.N / 16;
+    const bool fg_ok = xres_ok && q.N % 16 == 0 && q.t_pad <= 6 && fg_tiles <= 2 * cus &&
+                       (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * (2 * (int64_t)q.K + 16) <= STREAM_FG_LDS_MAX;
+    // Default: resident rows wherever they apply.  (Until the prefetch depths came down to 2 stages this form lost on short launches -- at 6
+    // stages the 4096 x 4096 o projection of a 6-tenant step was +25 % -- and was dispatched by size; at 2 stages it wins on every eligible
+    // launch: 6 tenants 4.805 -> 4.770 ms per step with o included, profiles/r04_decode_step_ab.txt.)  The hand-off consumer needs them
+    // whatever the flags say.
+    const bool xres_auto = STREAM_XRES_DEFAULT != 0;
+    const bool xres = xres_ok && ((g_stream_tune & 64) ? true : (g_stream_tune & 128) ? false : xres_auto);
+    // The fine grid is a resident-row form: decided only for launches that take one (the consumer or `xres`), so a launch that falls
+    // through to the per-stage forms below keeps its own column split (cpb) and LDS layout.
+    const bool fg = fg_ok && (q.ssq_in || xres) && !(g_stream_tune & 256) &&
+                    ((g_stream_tune & 512) ? true : (STREAM_FG_DEFAULT != 0 && fg_tiles > cus));
+    // Two-pass resident rows (FG = 2, round 6; gemv_stream_kernel): rows that do not fit LDS at once -- the down projection of a multi-tenant
+    // step, 6 x 14336 -- with ONE tile per block, every wave's k quarter cut in two halves.  Bit-identical to the per-stage-load form and
+    // SLOWER (down 33.0 -> 37.1 us at 2 stages of prefetch, 40.0 at 4; step +4 ... +6 %: profiles/r06_decode_step.txt), so like every A/B
+    // loser it exists in harness builds only (-DBD_AB_VARIANTS; bd_set_stream_tuning 8192 = on, + 16384 = 2 stages instead of 4).
+#ifdef BD_AB_VARIANTS
+    const bool fg2 = (g_stream_tune & 8192) && q.w_tiled == 1 && !q.norm_w && !q.ssq_in && q.epilogue == 0 && q.M == 1 && q.t_pad <= 8 && q.N % 16 == 0 &&
+                     fg_tiles <= cus && q.K % 1024 == 0 && q.K >= 8192 && (int64_t)q.B * q.K > 16 * 2048 && (int64_t)q.B * (q.K / 2) <= 24 * 2048 &&
+                     (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * ((int64_t)q.K + 16) <= STREAM_LDS_MAX;
+    if (fg2) {
+        f.XL = 2; f.FG = 2; f.AUX = 2; f.NS = (g_stream_tune & 16384) ? 2 : 4;
+        pl.cpb = 16; pl.grid = (unsigned)fg_tiles; pl.xs_off = (uint32_t)STREAM_FG_XS_OFF; pl.xrow = (uint32_t)q.K + 16u;
+        pl.form = 2;
+        stream_plan_lds(pl, q.B * q.M);
+        return pl;
+    }
+#endif
+    if (q.ssq_in && !xres_ok) { pl.rc = BD_E_BAD_SHAPE; return pl; }
+    if (q.ssq_in || xres) {
+        // resident rows (XL = 2), or RMSNorm by hand-off (XL = 3): the resident-row form with the rows pre-multiplied by the norm weight and
+        // the row scale in the epilogue; same envelope as the resident rows, nothing else implements it
+        // (A/B, not shipped: the short 6-tenant launches -- q|k|v, o -- on 8-wave blocks, half the stages per wave, are 1 % faster on the
+        //  step, 4.688 -> 4.639 ms, but 8 partial sums in another order are no longer bit-identical to every other form of the Linear:
+        //  profiles/r04_decode_step_ab.txt.  The kernel template still takes NW = 8 with XL = 2.)
+        f.XL = q.ssq_in ? 3 : 2; f.AUX = 2;
+        if (fg) { f.FG = 1; pl.cpb = 16; pl.grid = (unsigned)fg_tiles; pl.xs_off = (uint32_t)STREAM_FG_XS_OFF; pl.form = 1; }
+    } else {
+        f.XL = q.norm_w ? 1 : 0;
+        f.AUX = (q.w_tiled && wnt) ? 2 : 0;
+    }
+    f.NS = stream_depth(f.PK, f.XL, f.NM, f.WT);
+    stream_plan_lds(pl, q.B * q.M);
+    return pl;
+}
+
 int launch_gemv_stream_chunk(const Problem& q) {
-    constexpr int WTV = W8 == 2 ? 3 : W8 ? 2 : 1;              // gemv_stream_kernel's WT of a tile-major launch
-    // Prefetch depth of the int8 forms: a stage carries HALF the weight bytes, and what saturates HBM is bytes in flight per wave, not stages.
-    // With one or two tenants the int8 launches ran latency-bound at the 16-bit depths and twice the stages put the same bytes in flight
-    // (1 tenant, gate|up 31.3 -> 26.8 us, step 2.55 -> 2.31 ms); from 4 tenants on the sign work bounds the stage, the deeper queue only adds
-    // latency (6 tenants: q|k|v 17.4 -> 18.8 us, o 13.0 -> 14.1) and the norm-prologue form spills: same depth as 16 bits
-    // (rocprofv3 kernel traces, profiles/w8_decode_step.txt).
-    // The 4-bit forms follow the same rule with a QUARTER of the weight bytes per stage: one or two tenants run four times the 16-bit depth where
-    // the activation rows are resident (a stage is 3 loads: nibbles, group parameters, signs -- 8 stages keep 21 loads in flight, far inside the
-    // 6-bit vmcnt) and twice where every stage also loads its four activation fragments (7 loads per stage: 4 x 3 stages would need 77 counts);
-    // from 4 tenants on the 16-bit depth, for int8's measured reason.
-#define BD_W8NS(NM, NS) ((W8 && (NM) <= 2) ? (W8 == 2 ? 4 : 2) * (NS) : (NS))
-#define BD_W8NSP(NM, NS) ((W8 && (NM) <= 2) ? 2 * (NS) : (NS))
     StreamParams sp{};
     sp.wscale = q.wscale;
-    if constexpr (W8 == 2) {
+    if (q.w_tiled == 3) {
         const uint32_t m = (uint32_t)(q.q4_group / 128);
         sp.q4p = q.q4p;
         sp.q4_ngrp = (uint32_t)(q.K / q.q4_group);
         sp.q4_bytes = (uint32_t)((int64_t)(q.N / 16) * sp.q4_ngrp * 64);
         sp.q4_magic = m > 1 ? (uint32_t)((1ull << 32) / m) + 1u : 0u;
     }
-    t_last_decode_form = 0;
-    GemvParams& gp = sp.g;
-    gp.X = (const unsigned short*)q.A;
-    gp.P = (const uint32_t*)q.P;
-    gp.W = (const unsigned short*)q.W;
-    gp.alpha = q.alpha;
-    gp.C = q.C;
-    gp.ws = nullptr; gp.tickets = nullptr;
-    gp.B = q.B; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.R = q.B * q.M;
-    gp.sXb = q.sAb; gp.sPb = q.sPb; gp.sCb = q.sCb;
-    gp.sXm = (int)q.sAm; gp.sCm = (int)q.sCm; gp.ldw = (int)q.ldw; gp.sAlb = (int)q.sAlb; gp.gsz = q.N / q.G;
-    gp.KS = 1; gp.kslice = q.K;
-    gp.round_mode = q.round_mode; gp.accumulate = q.accumulate; gp.out_f32 = (q.out_dtype == BD_F32);
+    sp.g = gemv_params(q);
     const int nmask = q.sPb == 0 ? 1 : q.B;
-    // columns per block: the whole chip streams one launch, so every CU gets ~N / CUs columns (rounded up to whole sign-word
-    // quads); a few more blocks than CUs would serialise a second, nearly empty round
-    const int cus = num_cus();
-    int cpb = (q.N + cus - 1) / cus;
-    cpb = (cpb + 3) & ~3;
-    if (cpb < 4) cpb = 4;
-    if (g_forced_variant > 600 && g_forced_variant <= 664) cpb = 4 * (g_forced_variant - 600);     // test hook: 600 + cpb/4
-    sp.cpb = cpb;
+    const StreamPlan pl = stream_plan(q, num_cus());
+    sp.cpb = pl.cpb; sp.xs_off = pl.xs_off; sp.xrow = pl.xrow;
     sp.pts = q.mask_tiled == 1 ? 16u * (uint32_t)(q.K / 32) : 16u;
     sp.prs = q.mask_tiled == 1 ? 16u : (uint32_t)q.N;
     sp.tp = (uint32_t)q.t_pad;
@@ -497,199 +686,30 @@ int launch_gemv_stream_chunk(const Problem& q) {
     sp.nw_next = (const unsigned short*)q.nw_next; sp.sNwNext = q.sNwNext; sp.xw_out = (unsigned short*)q.xw_out;
     sp.no_res_prefetch = (g_stream_tune & 1024) ? 1 : 0;
     sp.n_bytes = q.norm_w ? (uint32_t)(((int64_t)(q.B - 1) * q.sNw + q.K) * 2) : 0u;
-    sp.xs_off = (uint32_t)STREAM_XS_OFF; sp.xrow = (uint32_t)q.K * 2u + 16u;
     sp.jsh = 0;
     while ((2048 << sp.jsh) < q.K) ++sp.jsh;
-    if (q.epilogue == 1 || q.ssq_out) { cpb = (cpb + 15) & ~15; sp.cpb = cpb; }      // whole [8 gate | 8 up] tiles / whole hand-off tiles per block
-    const unsigned grid = (unsigned)((q.N + cpb - 1) / cpb);
     sp.x_bytes = (uint32_t)(((int64_t)(q.B - 1) * q.sAb + (int64_t)(q.M - 1) * q.sAm + q.K) * 2);
     sp.w_bytes = q.W ? (uint32_t)(((int64_t)(q.N - 1) * q.ldw + q.K) * 2) : 0u;
-    if (q.w_tiled)       // tile-major W: [N/16][K/128] blocks of 4 KiB
-        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * (W8 == 2 ? 1024 : W8 ? 2048 : 4096));      // (int8: 2 KiB, 4-bit: 1 KiB)
+    if (q.w_tiled)       // tile-major W: [N/16][K/128] blocks of 4 KiB (int8: 2 KiB, 4-bit: 1 KiB)
+        sp.w_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * (q.w_tiled == 3 ? 1024 : q.w_tiled == 2 ? 2048 : 4096));
     sp.p_bytes = (uint32_t)(((int64_t)(nmask - 1) * q.sPb + (int64_t)(q.K / 32) * (q.mask_tiled ? (q.N + 15) / 16 * 16 : q.N)) * 4);
-    int rc;
-    if (q.mask_tiled == 2) {      // packed layout: all tenants of the call in one chunk, interleaved; extent from the pack's own geometry
+    if (q.mask_tiled == 2)      // packed layout: extent from the pack's own geometry
         sp.p_bytes = (uint32_t)((int64_t)((q.N + 15) / 16) * ((q.K + 127) / 128) * 4 * 16 * q.t_pad * 4);
 #ifdef BD_AB_VARIANTS
-        if (ring_wanted() && !W8) {      // loader / consumer kernel (variant 700); launches outside its envelope stay on the streaming kernel
-            RingParams rp{};
-            rp.g = gp; rp.cpb = cpb;
-            if (ring_plan(q, rp)) {
-                int rrc;
-                switch (q.t_pad) {
-                    case 1: rrc = launch_ring_inst<DT, 1>(rp, grid, q.st); break;
-                    case 2: rrc = launch_ring_inst<DT, 2>(rp, grid, q.st); break;
-                    case 4: rrc = launch_ring_inst<DT, 4>(rp, grid, q.st); break;
-                    case 6: rrc = launch_ring_inst<DT, 6>(rp, grid, q.st); break;
-                    default: rrc = launch_ring_inst<DT, 8>(rp, grid, q.st); break;
-                }
-                if (rrc != BD_OK) return rrc;
-                t_last_variant = 700;
-                return launch_status();
-            }
-            if (g_forced_variant == 700) return BD_E_BAD_SHAPE;
-        }
-        // kernel kinds: plain | RMSNorm prologue (XL) | XL + SwiGLU epilogue | SwiGLU epilogue only; each with row-major or tile-major W (WT)
-#else
-        if (g_forced_variant == 700) return BD_E_BAD_SHAPE;      // harness-only kernel (round 4 A/B loser): never silently replaced
-#endif
-        // tile-major W: optional nt policy on the weight loads (STREAM_WT_NT_DEFAULT, or bd_set_stream_tuning bit 4 = on / bit 5 = off)
-        const bool wnt = (g_stream_tune & 16) ? true : (g_stream_tune & 32) ? false : (STREAM_WT_NT_DEFAULT != 0);
-        // ... and optionally the activation rows resident in LDS with a deeper weight prefetch (XL = 2; bd_set_stream_tuning bit 6 = on,
-        // bit 7 = off): plain and SwiGLU launches with M = 1 and R * K <= 32768
-        // (any K: tile-major W already needs K % 128 == 0; the norm prologue keeps its power-of-two rule, this form does not need it)
-        // Every wave must own at least one 128-k iteration: a wave with an empty k range still walks one padded stage per tile, whose
-        // zero sign words expand to -1 fragments -- harmless against the zero activation fragments of the per-stage form, NOT against
-        // fragments read from the resident rows (K = 1152: 9 iterations over 4 waves leave the last wave empty).
-        const int nit_x = (q.K + 127) / 128;
-        const bool xres_ok = q.w_tiled && (!q.norm_w || q.ssq_in) && q.M == 1 && q.t_pad <= 8 && q.K >= 1024 && 3 * ((nit_x + 3) / 4) < nit_x &&
-                             (int64_t)q.B * q.K <= 16 * 2048 &&
-                             (int64_t)STREAM_XS_OFF + (int64_t)q.B * (2 * (int64_t)q.K + 16) <= STREAM_LDS_MAX;
-        // Fine grid (FG, round 6; gemv_stream_kernel): a resident-row launch whose 16-column tiles number between one and two per CU --
-        // Mistral's fused q|k|v: 384 tiles -- runs as ONE round of single-tile blocks, two per CU (<= 80 KB of LDS with the nibble sign table,
-        // <= 256 VGPRs), instead of 256 blocks that walk 1.5 tiles each.  bd_set_stream_tuning: 256 = never, 512 = every eligible launch
-        // with at most two tiles per CU (one tile per CU included: the o projection).
-        const int fg_tiles = q.N / 16;
-        const bool fg_ok = xres_ok && q.N % 16 == 0 && q.t_pad <= 6 && fg_tiles <= 2 * cus &&
-                           (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * (2 * (int64_t)q.K + 16) <= STREAM_FG_LDS_MAX;
-        // Default: resident rows wherever they apply.  (Until the prefetch depths came down to 2 stages this form lost on short launches -- at 6
-        // stages the 4096 x 4096 o projection of a 6-tenant step was +25 % -- and was dispatched by size; at 2 stages it wins on every eligible
-        // launch: 6 tenants 4.805 -> 4.770 ms per step with o included, profiles/r04_decode_step_ab.txt.)  The hand-off consumer needs them
-        // whatever the flags say.
-        const bool xres_auto = STREAM_XRES_DEFAULT != 0;
-        const bool xres = xres_ok && ((g_stream_tune & 64) ? true : (g_stream_tune & 128) ? false : xres_auto);
-        // The fine grid is a resident-row form: decided only for launches that take one (the consumer or `xres`), so a launch that falls
-        // through to the per-stage forms below keeps its own column split (cpb) and LDS layout.  t_last_decode_form is set where an FG
-        // instantiation is launched.
-        const bool fg = fg_ok && (q.ssq_in || xres) && !(g_stream_tune & 256) &&
-                        ((g_stream_tune & 512) ? true : (STREAM_FG_DEFAULT != 0 && fg_tiles > cus));
-        const unsigned fg_grid = (unsigned)fg_tiles;
-        // Two-pass resident rows (FG = 2, round 6; gemv_stream_kernel): rows that do not fit LDS at once -- the down projection of a multi-tenant
-        // step, 6 x 14336 -- with ONE tile per block, every wave's k quarter cut in two halves.  Bit-identical to the per-stage-load form and
-        // SLOWER (down 33.0 -> 37.1 us at 2 stages of prefetch, 40.0 at 4; step +4 ... +6 %: profiles/r06_decode_step.txt), so like every A/B
-        // loser it exists in harness builds only (-DBD_AB_VARIANTS; bd_set_stream_tuning 8192 = on, + 16384 = 2 stages instead of 4).
-#ifdef BD_AB_VARIANTS
-        const bool fg2 = (g_stream_tune & 8192) && q.w_tiled == 1 && !q.norm_w && !q.ssq_in && q.epilogue == 0 && q.M == 1 && q.t_pad <= 8 && q.N % 16 == 0 &&
-                         fg_tiles <= cus && q.K % 1024 == 0 && q.K >= 8192 && (int64_t)q.B * q.K > 16 * 2048 && (int64_t)q.B * (q.K / 2) <= 24 * 2048 &&
-                         (int64_t)STREAM_FG_XS_OFF + (int64_t)q.B * ((int64_t)q.K + 16) <= STREAM_LDS_MAX;
-        if (fg2) {
-            sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; sp.xrow = (uint32_t)q.K + 16u;
-            t_last_decode_form = 2;
-#define BD_X2(NM) rc = (g_stream_tune & 16384) ? launch_stream_inst<DT, NM, true, 2, 4, 1, 2, 1, 2, 0, 1, 2>(sp, dim3(fg_grid), q.st) \
-                                              : launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 2, 0, 1, 2>(sp, dim3(fg_grid), q.st)
-            switch (q.t_pad) {
-                case 4: BD_X2(4); break;
-                case 6: BD_X2(6); break;
-                default: return BD_E_BAD_SHAPE;
-            }
-#undef BD_X2
-            if (rc != BD_OK) return rc;
-            return launch_status();
-        }
-#endif
-        if (q.ssq_in) {
-            // RMSNorm by hand-off (XL = 3): the resident-row form with the rows pre-multiplied by the norm weight and the row scale in the
-            // epilogue; same envelope as the resident rows, nothing else implements it
-            if (!xres_ok) return BD_E_BAD_SHAPE;
-            if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
-#define BD_XH(NM) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 1, WTV, 1>(sp, dim3(fg_grid), q.st)   \
-                                             : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 0, WTV, 1>(sp, dim3(fg_grid), q.st))  \
-                     : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 1, WTV>(sp, dim3(grid), q.st)   \
-                                       : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, 2, 1, 3, 0, WTV>(sp, dim3(grid), q.st)
-            switch (q.t_pad) {
-                case 1: BD_XH(1); break;
-                case 2: BD_XH(2); break;
-                case 4: BD_XH(4); break;
-                case 6: BD_XH(6); break;
-                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 1, WTV>(sp, dim3(grid), q.st)
-                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 3, 0, WTV>(sp, dim3(grid), q.st); break;
-                default: return BD_E_BAD_SHAPE;
-            }
-#undef BD_XH
-            if (rc != BD_OK) return rc;
-            return launch_status();
-        }
-        if (xres) {
-            if (fg) { sp.cpb = 16; sp.xs_off = (uint32_t)STREAM_FG_XS_OFF; t_last_decode_form = 1; }
-#define BD_XR(NM, NS8) rc = fg ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, WTV, 1>(sp, dim3(fg_grid), q.st)   \
-                                                  : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, WTV, 1>(sp, dim3(fg_grid), q.st))  \
-                          : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 1, WTV>(sp, dim3(grid), q.st)   \
-                                            : launch_stream_inst<DT, NM, true, NS8, 4, 1, 2, 1, 2, 0, WTV>(sp, dim3(grid), q.st)
-            // (A/B, not shipped: the short 6-tenant launches -- q|k|v, o -- on 8-wave blocks, half the stages per wave, are 1 % faster on the
-            //  step, 4.688 -> 4.639 ms, but 8 partial sums in another order are no longer bit-identical to every other form of the Linear:
-            //  profiles/r04_decode_step_ab.txt.  The kernel template still takes NW = 8 with XL = 2.)
-            switch (q.t_pad) {
-                // Prefetch depth: TWO stages.  Same-process A/Bs of the whole step late in round 4 (profiles/r04_decode_step_ab.txt): 8 -> 6 -> 4
-                // -> 2 stages each made the step faster (1 tenant: 3.57 -> 3.32 ms over the whole sequence of changes; 6 tenants: -0.3 %
-                // for this form alone) -- the memory system is saturated by far fewer loads in flight than the register file can hold, and
-                // beyond that point a deeper queue only adds latency (returns are in issue order).  (The parity of NS selects the
-                // activation fragment set, so 2 is the minimum.)
-                case 1: BD_XR(1, BD_W8NS(1, 2)); break;
-                case 2: BD_XR(2, BD_W8NS(2, 2)); break;
-                case 4: BD_XR(4, BD_W8NS(4, 2)); break;
-                case 6: BD_XR(6, BD_W8NS(6, 2)); break;
-                case 8: rc = q.epilogue == 1 ? launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 1, WTV>(sp, dim3(grid), q.st)
-                                             : launch_stream_inst<DT, 8, true, 2, 4, 1, 2, 1, 2, 0, WTV>(sp, dim3(grid), q.st); break;
-                default: return BD_E_BAD_SHAPE;
-            }
-#undef BD_XR
-            if (rc != BD_OK) return rc;
-            return launch_status();
-        }
-// (tile-major weight: the norm-prologue forms run 2 stages deep -- 6 tenants: gate|up with its norm at 2 instead of 4 stages is -1 % on
-//  the whole step; the plain / SwiGLU-only forms NS4 stages)
-#define BD_PKW(NM, NS4, AX) (q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, AX, 1, 1, 1, WTV>(sp, dim3(grid), q.st)   \
-                                                         : launch_stream_inst<DT, NM, true, BD_W8NS(NM, 2), 4, 1, AX, 1, 1, 0, WTV>(sp, dim3(grid), q.st)) \
-                                      : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 1, WTV>(sp, dim3(grid), q.st)   \
-                                                        : launch_stream_inst<DT, NM, true, NS4, 4, 1, AX, 1, 0, 0, WTV>(sp, dim3(grid), q.st))
-#define BD_PK(NM, NS4) rc = q.w_tiled                                                                                                   \
-                     ? (wnt ? BD_PKW(NM, BD_W8NSP(NM, NS4), 2) : BD_PKW(NM, BD_W8NSP(NM, NS4), 0))                                                                \
-                     : q.norm_w ? (q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 1>(sp, dim3(grid), q.st)   \
-                                                        : launch_stream_inst<DT, NM, true, 2, 4, 1, 0, 1, 1, 0>(sp, dim3(grid), q.st))  \
-                     : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, NS4, 4, 1, 0, 1, 0, 1>(sp, dim3(grid), q.st)            \
-                     : q.W ? launch_stream_inst<DT, NM, true, NS4, 4, 1, 0, 1>(sp, dim3(grid), q.st)                              \
-                           : launch_stream_inst<DT, NM, false, NS4, 4, 1, 0, 1>(sp, dim3(grid), q.st)
-        switch (q.t_pad) {
-            // depth of the plain / SwiGLU-only forms: 1 tenant 3 stages (8 until late in round 4: -6 % on the single-delta step over 8 -> 6 -> 4
-            // -> 3), 2 tenants 4 (6: +3 %), 4 and more 4 (3 measured +0.6 % at 6 tenants)
-            case 1: BD_PK(1, 3); break;
-            case 2: BD_PK(2, 4); break;
-            case 4: BD_PK(4, 4); break;
-            case 6: BD_PK(6, 4); break;      // (NS 6 with nt weight loads measured 5-14 % slower: tools/ab_decode_depth.py)
-            case 8: BD_PK(8, 4); break;
-            // 9 .. 16 tenants in ONE launch (the reference publishes B = 16: notebooks/binary_gemm_kernel_triton.ipynb:759): plain and SwiGLU
-            // launches; the fused-norm / resident-row forms end at 8 rows of K = 4096 anyway
-#define BD_PKL(NM) rc = (q.norm_w || !q.W) ? BD_E_BAD_SHAPE                                                                             \
-                     : q.w_tiled ? (q.epilogue == 1 ? (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 1, WTV>(sp, dim3(grid), q.st)    \
-                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 1, WTV>(sp, dim3(grid), q.st))  \
-                                                    : (wnt ? launch_stream_inst<DT, NM, true, 4, 4, 1, 2, 1, 0, 0, WTV>(sp, dim3(grid), q.st)    \
-                                                            : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 0, WTV>(sp, dim3(grid), q.st))) \
-                     : q.epilogue == 1 ? launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1, 0, 1>(sp, dim3(grid), q.st)                     \
-                                       : launch_stream_inst<DT, NM, true, 4, 4, 1, 0, 1>(sp, dim3(grid), q.st)
-            case 12: BD_PKL(12); break;
-            case 16: BD_PKL(16); break;
-#undef BD_PKL
-            default: return BD_E_BAD_SHAPE;
-        }
-#undef BD_PK
-#undef BD_PKW
-#undef BD_W8NS
-#undef BD_W8NSP
-        if (rc != BD_OK) return rc;
+    if (pl.ring) {
+        t_last_plan = pl;
+        if (g_decode_dry_run) return BD_OK;
+        RingParams rp{};
+        rp.g = sp.g; rp.cpb = pl.cpb;
+        ring_plan(q, rp);
+        int rrc = BD_OK;
+        for_bucket<1, 2, 4, 6, 8>(q.t_pad, [&](auto NM) { rrc = launch_ring_inst<NM>(q.dtype, rp, pl.grid, q.st); });
+        if (rrc != BD_OK) return rrc;
+        t_last_variant = 700;
         return launch_status();
     }
-    // NS = stages of loads in flight per wave; bounded by the 256-VGPR budget of a 2-waves-per-SIMD block (hipcc spills beyond)
-#define BD_STREAM(NM, NS4) rc = q.W ? launch_stream_tuned<DT, NM, true, NS4>(sp, dim3(grid), q.st) \
-                                     : launch_stream_tuned<DT, NM, false, NS4>(sp, dim3(grid), q.st)
-    if (nmask <= 1) BD_STREAM(1, 8);
-    else if (nmask <= 2) BD_STREAM(2, 6);
-    else if (nmask <= 3) BD_STREAM(3, 4);
-    else if (nmask <= 4) BD_STREAM(4, 4);
-    else if (nmask <= 6) BD_STREAM(6, 4);
-    else BD_STREAM(8, 4);
-#undef BD_STREAM
-    if (rc != BD_OK) return rc;
-    return launch_status();
+#endif
+    return launch_stream(pl, sp, q.st);
 }
 
 // batches of more than 16 activation rows run as consecutive launches over chunks of floor(16 / M) batch entries (each chunk streams
@@ -777,7 +797,7 @@ template <int DT>
 int launch_gemv(const Problem& q, bool valu_form, bool col16 = false, bool stream = false) {
     const int cb = GEMV_MAX_R / q.M;
     auto one = [&](const Problem& c) {
-        return stream ? launch_gemv_stream_chunk<DT>(c) : col16 ? launch_gemv_col16_chunk<DT>(c) : launch_gemv_chunk<DT>(c, valu_form);
+        return stream ? launch_gemv_stream_chunk(c) : col16 ? launch_gemv_col16_chunk<DT>(c) : launch_gemv_chunk<DT>(c, valu_form);
     };
     if (q.B <= cb) return one(q);
     const int esz = q.out_dtype == BD_F32 ? 4 : 2;
@@ -796,19 +816,9 @@ int launch_gemv(const Problem& q, bool valu_form, bool col16 = false, bool strea
 
 template <int DT>
 int launch_gemv_chunk(const Problem& q, bool valu_form) {
-    GemvParams gp;
-    gp.X = (const unsigned short*)q.A;
-    gp.P = (const uint32_t*)q.P;
-    gp.W = (const unsigned short*)q.W;
-    gp.alpha = q.alpha;
-    gp.C = q.C;
+    GemvParams gp = gemv_params(q);
     gp.ws = (float*)q.ws;
-    gp.B = q.B; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.R = q.B * q.M;
-    gp.sXb = q.sAb; gp.sPb = q.sPb; gp.sCb = q.sCb;
-    gp.sXm = (int)q.sAm; gp.sCm = (int)q.sCm; gp.ldw = (int)q.ldw; gp.sAlb = (int)q.sAlb; gp.gsz = q.N / q.G;
     gemv_split(q, gp.KS, gp.kslice);
-    gp.round_mode = q.round_mode; gp.accumulate = q.accumulate; gp.out_f32 = (q.out_dtype == BD_F32);
-    gp.tickets = nullptr;
     if (gp.KS > 1) {
         const int64_t need = GEMV_TICKET_BYTES + (int64_t)gp.KS * gp.R * q.N * 4;
         if (!q.ws || q.ws_bytes < need) return BD_E_WORKSPACE;
@@ -817,25 +827,11 @@ int launch_gemv_chunk(const Problem& q, bool valu_form) {
         if ((q.N + 63) / 64 <= GEMV_TICKET_BYTES / 4 && !g_gemv_two_launch) gp.tickets = (uint32_t*)q.ws;
     }
     if (valu_form) {
-        const int R = gp.R;      // rows >= R are computed and discarded, so the buckets are kept fine-grained
-        if (R <= 1) launch_gemv_valu<DT, 1>(q, gp);
-        else if (R <= 2) launch_gemv_valu<DT, 2>(q, gp);
-        else if (R <= 3) launch_gemv_valu<DT, 3>(q, gp);
-        else if (R <= 4) launch_gemv_valu<DT, 4>(q, gp);
-        else if (R <= 6) launch_gemv_valu<DT, 6>(q, gp);
-        else if (R <= 8) launch_gemv_valu<DT, 8>(q, gp);
-        else if (R <= 12) launch_gemv_valu<DT, 12>(q, gp);
-        else launch_gemv_valu<DT, 16>(q, gp);
+        // rows >= R are computed and discarded, so the buckets are kept fine-grained
+        for_bucket<1, 2, 3, 4, 6, 8, 12, 16>(gp.R, [&](auto RMAX) { launch_gemv_valu<DT, RMAX>(q, gp); });
     } else {
-        const int nm = q.sPb == 0 ? 1 : q.B;     // accumulator sets = distinct masks (extra sets of a bucket repeat the last mask)
-        if (nm <= 1) launch_gemv_mfma<DT, 1>(q, gp);
-        else if (nm <= 2) launch_gemv_mfma<DT, 2>(q, gp);
-        else if (nm <= 3) launch_gemv_mfma<DT, 3>(q, gp);
-        else if (nm <= 4) launch_gemv_mfma<DT, 4>(q, gp);
-        else if (nm <= 6) launch_gemv_mfma<DT, 6>(q, gp);
-        else if (nm <= 8) launch_gemv_mfma<DT, 8>(q, gp);
-        else if (nm <= 12) launch_gemv_mfma<DT, 12>(q, gp);
-        else launch_gemv_mfma<DT, 16>(q, gp);
+        // accumulator sets = distinct masks (extra sets of a bucket repeat the last mask)
+        for_bucket<1, 2, 3, 4, 6, 8, 12, 16>(q.sPb == 0 ? 1 : q.B, [&](auto NM) { launch_gemv_mfma<DT, NM>(q, gp); });
     }
     if (gp.KS > 1 && !gp.tickets) {
         dim3 g2((unsigned)((q.N + 255) / 256), (unsigned)gp.R);
@@ -1357,6 +1353,17 @@ int dispatch(const Problem& q) {
 
 }  // namespace
 
+extern "C" int bd_last_decode_form(void) { return t_last_plan.form; }
+extern "C" int bd_set_decode_dry_run(int on) { g_decode_dry_run = on ? 1 : 0; return BD_OK; }
+extern "C" int bd_last_decode_plan(int32_t* out, int n) {
+    const StreamPlan& pl = t_last_plan;
+    const StreamForm& f = pl.f;
+    const int32_t rec[BD_DECODE_PLAN_INTS] = {pl.rc, f.DT, f.NM, f.HASW, f.NS, f.NW, f.WNAT, f.AUX, f.PK, f.XL, f.EPI, f.WT, f.FG, (int32_t)pl.grid,
+                                              (int32_t)pl.grid_y, pl.block, pl.lds, pl.cpb, (int32_t)pl.xs_off, (int32_t)pl.xrow, pl.form};
+    for (int i = 0; out && i < n && i < BD_DECODE_PLAN_INTS; ++i) out[i] = rec[i];
+    return BD_DECODE_PLAN_INTS;
+}
+
 extern "C" int64_t bd_gemm_workspace_bytes(int B, int M, int N, int K) {
     if (B <= 0 || M <= 0 || N <= 0 || K <= 0) return 0;
     if (M > GEMV_MAX_M || (int64_t)B * M > 4 * GEMV_MAX_R) {
@@ -1416,39 +1423,25 @@ extern "C" int bd_delta_bmm(const void* A, const int32_t* P, void* C, int B, int
     return dispatch(q);
 }
 
-// int8 base weight (bd_binary_linear_decode_w8): the streaming decode kernel and nothing else -- a forced variant other than the
-// streaming kernel's own test hooks is refused, like every launch no kernel implements
-static int dispatch_w8(const Problem& q) {
+// int8 / 4-bit base weight (bd_binary_linear_decode_w8 / _q4: q.w_tiled 2 / 3, the kernel's WT): the streaming decode kernel and nothing else --
+// a forced variant other than the streaming kernel's own test hooks is refused, like every launch no kernel implements
+static int dispatch_quant(const Problem& q) {
     if (q.dtype != BD_F16 && q.dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (q.out_dtype != q.dtype && q.out_dtype != BD_F32) return BD_E_BAD_DTYPE;
     if (q.G < 1 || q.N % q.G) return BD_E_BAD_GROUPS;
     if (!q.A || !q.P || !q.C || !q.alpha) return BD_E_NULL;
     if (g_forced_variant >= 0 && !(g_forced_variant >= 600 && g_forced_variant <= 664)) return BD_E_BAD_SHAPE;
     t_last_variant = 600;
-    return q.dtype == BD_BF16 ? launch_gemv_stream_chunk<DT_BF16, 1>(q) : launch_gemv_stream_chunk<DT_F16, 1>(q);
+    return launch_gemv_stream_chunk(q);
 }
 
-// 4-bit GPTQ base weight (bd_binary_linear_decode_q4): as dispatch_w8, the WT = 3 instantiations
-static int dispatch_q4(const Problem& q) {
-    if (q.dtype != BD_F16 && q.dtype != BD_BF16) return BD_E_BAD_DTYPE;
-    if (q.out_dtype != q.dtype && q.out_dtype != BD_F32) return BD_E_BAD_DTYPE;
-    if (q.G < 1 || q.N % q.G) return BD_E_BAD_GROUPS;
-    if (!q.A || !q.P || !q.C || !q.alpha) return BD_E_NULL;
-    if (g_forced_variant >= 0 && !(g_forced_variant >= 600 && g_forced_variant <= 664)) return BD_E_BAD_SHAPE;
-    t_last_variant = 600;
-    return q.dtype == BD_BF16 ? launch_gemv_stream_chunk<DT_BF16, 2>(q) : launch_gemv_stream_chunk<DT_F16, 2>(q);
-}
-
+// `q` arrives with what the entry point fuses around the Linear or says about its base weight, filled by name: norm_w / sNw / eps / epilogue,
+// ssq_in / ssq_out / xw_out, pn_*, and wscale (int8: its presence is the signal) or q4p / q4_group (4-bit); everything else is set here.
 static int binary_linear_impl(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B, int M,
                               int N, int K, int64_t sXb, int64_t sXm, int64_t ldw, int64_t sPb, int64_t sAlb, int G,
                               int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, int mask_tiled, int t_pad,
-                              void* ws, int64_t ws_bytes, void* stream, const void* norm_w = nullptr, int64_t sNw = 0,
-                              float eps = 0.f, int epilogue = 0, const float* ssq_in = nullptr, float* ssq_out = nullptr,
-                              void* xw_out = nullptr, const void* pn_w = nullptr, int64_t s_pnw = 0, float pn_eps = 0.f, void* pn_h = nullptr,
-                              int64_t sHb = 0, int64_t sHm = 0, const float* wscale = nullptr, bool w8 = false, const uint32_t* q4p = nullptr,
-                              int q4_group = 0) {
+                              void* ws, int64_t ws_bytes, void* stream, Problem q = {}) {
     if (B > 0 && M > 0 && N > 0 && !W) return BD_E_NULL;
-    Problem q{};
     q.A = X; q.P = P; q.C = Y; q.W = W; q.alpha = alpha;
     q.B = B; q.M = M; q.N = N; q.K = K;
     q.sAb = sXb; q.sAm = sXm; q.sPb = sPb; q.sCb = sYb; q.sCm = sYm; q.ldw = ldw; q.sAlb = sAlb;
@@ -1460,44 +1453,39 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
         q.w_tiled = 1;
         q.ldw = K;            // (extent checks below; the kernel does not use it)
     }
-    if (w8) {                 // int8 tile-major base weight + row scales: the tile-major envelope, nothing else (no row-major int8 form)
-        if (!q.w_tiled || !wscale || B < 1 || B > GEMV_MAX_R || !aligned16(wscale)) return BD_E_BAD_SHAPE;
+    if (q.wscale) {           // int8 tile-major base weight + row scales: the tile-major envelope, nothing else (no row-major int8 form)
+        if (!q.w_tiled || B < 1 || B > GEMV_MAX_R || !aligned16(q.wscale)) return BD_E_BAD_SHAPE;
         q.w_tiled = 2;
-        q.wscale = wscale;
     }
-    if (q4_group) {           // 4-bit GPTQ tile-major base weight + packed group parameters: the tile-major envelope, nothing else
-        if (w8 || !q.w_tiled || !q4p || B < 1 || B > GEMV_MAX_R || !aligned16(q4p) || !aligned16(W)) return BD_E_BAD_SHAPE;
-        if (q4_group < 128 || q4_group % 128 || K % q4_group || K / 128 >= 65536) return BD_E_BAD_SHAPE;
+    if (q.q4_group) {           // 4-bit GPTQ tile-major base weight + packed group parameters: the tile-major envelope, nothing else
+        if (q.wscale || !q.w_tiled || !q.q4p || B < 1 || B > GEMV_MAX_R || !aligned16(q.q4p) || !aligned16(W)) return BD_E_BAD_SHAPE;
+        if (q.q4_group < 128 || q.q4_group % 128 || K % q.q4_group || K / 128 >= 65536) return BD_E_BAD_SHAPE;
         q.w_tiled = 3;
-        q.q4p = q4p; q.q4_group = q4_group;
     }
-    q.norm_w = norm_w; q.sNw = sNw; q.eps = eps; q.epilogue = epilogue;
-    q.pn_w = pn_w; q.s_pnw = s_pnw; q.pn_eps = pn_eps; q.pn_h = pn_h; q.sHb = sHb; q.sHm = sHm;
-    q.ssq_in = ssq_in; q.ssq_out = ssq_out;
-    if (ssq_in || ssq_out || xw_out) {
+    if (q.ssq_in || q.ssq_out || q.xw_out) {
         // RMSNorm hand-off (gemv_stream_kernel, StreamParams::ssq_in / ssq_out / xw_out): packed layout, one row per tenant, <= 8 tenants
-        if (mask_tiled != 2 || M != 1 || B > 8 || (ssq_in && ssq_out)) return BD_E_BAD_SHAPE;
-        if (ssq_in && (norm_w || !aligned16(ssq_in) || K % 16 || K > 16 * 256 * 2)) return BD_E_BAD_SHAPE;   // (X = the producer's pre-multiplied copy)
-        if (ssq_out && (N % 16 || out_dtype == BD_F32 || epilogue || !aligned16(ssq_out))) return BD_E_BAD_SHAPE;
-        if (xw_out && (!ssq_out || !norm_w || sNw < 0)) return BD_E_BAD_SHAPE;
-        if (ssq_out && norm_w && !xw_out) return BD_E_BAD_SHAPE;
-        if (ssq_out) {            // the producer's norm_w is the NEXT norm's weight (epilogue multiply), not a prologue on its own input
-            q.nw_next = norm_w; q.sNwNext = sNw; q.xw_out = xw_out;
-            q.norm_w = nullptr; norm_w = nullptr;
+        if (mask_tiled != 2 || M != 1 || B > 8 || (q.ssq_in && q.ssq_out)) return BD_E_BAD_SHAPE;
+        if (q.ssq_in && (q.norm_w || !aligned16(q.ssq_in) || K % 16 || K > 16 * 256 * 2)) return BD_E_BAD_SHAPE;   // (X = the producer's pre-multiplied copy)
+        if (q.ssq_out && (N % 16 || out_dtype == BD_F32 || q.epilogue || !aligned16(q.ssq_out))) return BD_E_BAD_SHAPE;
+        if (q.xw_out && (!q.ssq_out || !q.norm_w || q.sNw < 0)) return BD_E_BAD_SHAPE;
+        if (q.ssq_out && q.norm_w && !q.xw_out) return BD_E_BAD_SHAPE;
+        if (q.ssq_out) {            // the producer's norm_w is the NEXT norm's weight (epilogue multiply), not a prologue on its own input
+            q.nw_next = q.norm_w; q.sNwNext = q.sNw;
+            q.norm_w = nullptr;
         }
     }
-    if (norm_w || epilogue) {
+    if (q.norm_w || q.epilogue) {
         // fused prologue / epilogue of the packed streaming kernel: see gemv_stream_kernel (XL, EPI)
-        if (mask_tiled != 2 || (epilogue != 0 && epilogue != 1)) return BD_E_BAD_SHAPE;
-        if (norm_w) {
-            if (!aligned16(norm_w) || sNw % 8 || sNw < 0) return BD_E_BAD_SHAPE;
+        if (mask_tiled != 2 || (q.epilogue != 0 && q.epilogue != 1)) return BD_E_BAD_SHAPE;
+        if (q.norm_w) {
+            if (!aligned16(q.norm_w) || q.sNw % 8 || q.sNw < 0) return BD_E_BAD_SHAPE;
             // one row per tenant (M == 1: the decode step), K = 2048 * 2^s, all rows in 16 x 16-byte chunks per thread
             // (the hand-off form needs no power of two: its copy is flat)
-            if (M != 1 || K < 2048 || (!ssq_in && (K & (K - 1))) || (int64_t)B * K > 16 * 2048) return BD_E_BAD_SHAPE;
+            if (M != 1 || K < 2048 || (!q.ssq_in && (K & (K - 1))) || (int64_t)B * K > 16 * 2048) return BD_E_BAD_SHAPE;
             if ((int64_t)STREAM_XS_OFF + (int64_t)B * M * (2 * (int64_t)K + 16) > STREAM_LDS_MAX) return BD_E_BAD_SHAPE;
-            if ((int64_t)(B - 1) * sNw + K >= (1ll << 30)) return BD_E_BAD_SHAPE;
+            if ((int64_t)(B - 1) * q.sNw + K >= (1ll << 30)) return BD_E_BAD_SHAPE;
         }
-        if (epilogue && (N % 16 || G != 2 || out_dtype != dtype || accumulate)) return BD_E_BAD_SHAPE;
+        if (q.epilogue && (N % 16 || G != 2 || out_dtype != dtype || accumulate)) return BD_E_BAD_SHAPE;
     }
     q.ws = ws; q.ws_bytes = ws_bytes; q.st = (hipStream_t)stream;
     // tile-major masks exist for the streaming decode kernel only (serving-side repack; the reference layout works everywhere)
@@ -1518,8 +1506,7 @@ static int binary_linear_impl(const void* X, const void* W, const int32_t* P, co
     // noise next to the GEMM and stays with the caller)
     // Y += ... (residual epilogue): the decode kernels and the one-pass fused tile kernels (M > 16 on their fast path)
     if (q.accumulate && !gemv_ok(q) && !(M > 16 && fast_ok(q))) return BD_E_BAD_SHAPE;
-    if (q.w_tiled == 2) return dispatch_w8(q);
-    if (q.w_tiled == 3) return dispatch_q4(q);
+    if (q.w_tiled >= 2) return dispatch_quant(q);
     return dispatch(q);
 }
 
@@ -1564,8 +1551,10 @@ extern "C" int bd_binary_linear_decode_fused(const void* X, const void* W, const
                                              void* stream) {
     if (!norm_w && epilogue != 1) return BD_E_NULL;
     if (B < 1 || M < 1 || N < 1 || K < 1) return BD_E_BAD_SHAPE;
+    Problem e{};
+    e.norm_w = norm_w; e.sNw = s_norm; e.eps = eps; e.epilogue = epilogue;
     return binary_linear_impl(X, W, P, alpha, Y, B, M, N, K, sXb, sXm, ldw, sPb, sAlb, G, sYb, sYm, dtype, out_dtype, accumulate, 2,
-                              t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue);
+                              t_pad, nullptr, 0, stream, e);
 }
 
 extern "C" int bd_binary_linear_decode_handoff(const void* X, const void* W, const int32_t* P, int t_pad, const float* alpha, void* Y,
@@ -1575,8 +1564,11 @@ extern "C" int bd_binary_linear_decode_handoff(const void* X, const void* W, con
                                                const float* ssq_in, float* ssq_out, void* xw_out, void* stream) {
     if (!ssq_in && !ssq_out) return BD_E_NULL;
     if (B < 1 || M < 1 || N < 1 || K < 1) return BD_E_BAD_SHAPE;
+    Problem e{};
+    e.norm_w = norm_w; e.sNw = s_norm; e.eps = eps; e.epilogue = epilogue;
+    e.ssq_in = ssq_in; e.ssq_out = ssq_out; e.xw_out = xw_out;
     return binary_linear_impl(X, W, P, alpha, Y, B, M, N, K, sXb, sXm, ldw, sPb, sAlb, G, sYb, sYm, dtype, out_dtype, accumulate, 2,
-                              t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out);
+                              t_pad, nullptr, 0, stream, e);
 }
 
 extern "C" int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const float* wscale, const int32_t* P, int t_pad, const float* alpha,
@@ -1586,9 +1578,12 @@ extern "C" int bd_binary_linear_decode_w8(const void* X, const int8_t* W8, const
                                           void* stream) {
     if (B < 1 || M != 1 || N < 1 || K < 1 || N % 16 || K % 128) return BD_E_BAD_SHAPE;      // (no row-major int8 form, no M > 1 form)
     if (!W8 || !wscale) return BD_E_NULL;
+    Problem e{};
+    e.norm_w = norm_w; e.sNw = s_norm; e.eps = eps; e.epilogue = epilogue;
+    e.ssq_in = ssq_in; e.ssq_out = ssq_out; e.xw_out = xw_out;
+    e.wscale = wscale;
     return binary_linear_impl(X, W8, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
-                              accumulate, 2, t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out, nullptr, 0, 0.f,
-                              nullptr, 0, 0, wscale, true);
+                              accumulate, 2, t_pad, nullptr, 0, stream, e);
 }
 
 extern "C" int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, const uint32_t* qparams, int group_size, const int32_t* P, int t_pad,
@@ -1599,9 +1594,12 @@ extern "C" int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, cons
     if (B < 1 || M != 1 || N < 1 || K < 1 || N % 16 || K % 128) return BD_E_BAD_SHAPE;      // (no row-major 4-bit form, no M > 1 form)
     if (group_size < 128 || group_size % 128 || K % group_size) return BD_E_BAD_SHAPE;      // (a 128-k stage lies inside one group)
     if (!W4 || !qparams) return BD_E_NULL;
+    Problem e{};
+    e.norm_w = norm_w; e.sNw = s_norm; e.eps = eps; e.epilogue = epilogue;
+    e.ssq_in = ssq_in; e.ssq_out = ssq_out; e.xw_out = xw_out;
+    e.q4p = qparams; e.q4_group = group_size;
     return binary_linear_impl(X, W4, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
-                              accumulate, 2, t_pad, nullptr, 0, stream, norm_w, s_norm, eps, epilogue, ssq_in, ssq_out, xw_out, nullptr, 0, 0.f,
-                              nullptr, 0, 0, nullptr, false, qparams, group_size);
+                              accumulate, 2, t_pad, nullptr, 0, stream, e);
 }
 
 extern "C" int bd_binary_linear_residual(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B,
@@ -1628,8 +1626,10 @@ extern "C" int bd_binary_linear_residual_norm(const void* X, const void* W, cons
         !aligned16(norm_w) || sYb != (int64_t)M * sYm || sHb != (int64_t)M * sHm)
         return BD_E_BAD_SHAPE;
     t_post_norm_done = 0;
+    Problem e{};
+    e.pn_w = norm_w; e.s_pnw = s_nw; e.pn_eps = eps; e.pn_h = H; e.sHb = sHb; e.sHm = sHm;
     const int rc = binary_linear_impl(X, W, P, alpha, Y, B, M, N, K, sXb, sXm, ldw, sPb, sAlb, G, sYb, sYm, dtype, dtype, 1, 0, 0, ws, ws_bytes,
-                                      stream, nullptr, 0, 0.f, 0, nullptr, nullptr, nullptr, norm_w, s_nw, eps, H, sHb, sHm);
+                                      stream, e);
     if (rc != BD_OK || t_post_norm_done) return rc;
     return bd_srv_rmsnorm(Y, norm_w, H, B * M, N, sYm, sHm, s_nw, M, eps, dtype, stream);
 }
@@ -1665,20 +1665,19 @@ extern "C" int bd_tenant_linear(const void* X, const void* W, void* Y, int T, in
     cpb = (cpb + 3) & ~3;
     if (cpb < 4) cpb = 4;
     sp.cpb = cpb;
-    dim3 grid((unsigned)((N + cpb - 1) / cpb), (unsigned)T);
-    hipStream_t st = (hipStream_t)stream;
+    StreamPlan pl;
+    StreamForm& f = pl.f;
+    f.DT = dtype == BD_BF16 ? DT_BF16 : DT_F16;
+    f.PK = f.WT = f.XL = f.FG = f.NM = f.EPI = 0; f.HASW = 1; f.NW = 4;
+    f.NS = stream_depth(0, 0, 0, 0);
     // A/B (round 6; bd_set_stream_tuning bits 11 / 12): natural-order weight loads (a load instruction = 16 rows x 64 contiguous bytes) with / without the
     // non-temporal policy, against the shipped word-row order.  profiles/r06_decode_step.txt has the outcome.
-    int rc;
-    if (g_stream_tune & 2048)
-        rc = dtype == BD_BF16 ? launch_stream_inst<DT_BF16, 0, true, 8, 4, 1, 2>(sp, grid, st) : launch_stream_inst<DT_F16, 0, true, 8, 4, 1, 2>(sp, grid, st);
-    else if (g_stream_tune & 4096)
-        rc = dtype == BD_BF16 ? launch_stream_inst<DT_BF16, 0, true, 8, 4, 1, 0>(sp, grid, st) : launch_stream_inst<DT_F16, 0, true, 8, 4, 1, 0>(sp, grid, st);
-    else
-        rc = dtype == BD_BF16 ? launch_stream_tuned<DT_BF16, 0, true, 8>(sp, grid, st)
-                              : launch_stream_tuned<DT_F16, 0, true, 8>(sp, grid, st);      // (NS 6 / 4 measured equal or slower here)
-    if (rc != BD_OK) return rc;
-    return launch_status();
+    f.WNAT = (g_stream_tune & (2048 | 4096)) ? 1 : 0;
+    f.AUX = (g_stream_tune & 2048) ? 2 : 0;
+    if (STREAM_AB && !f.WNAT) stream_plan_tuned(f);
+    pl.cpb = cpb; pl.grid = (unsigned)((N + cpb - 1) / cpb); pl.grid_y = (unsigned)T;
+    stream_plan_lds(pl, M);
+    return launch_stream(pl, sp, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ serving-loop glue (decode step; callers of the path)

@@ -72,6 +72,17 @@ int bd_set_stream_tuning(int flags);
  * bits 11 / 12: bd_tenant_linear's weight loads in natural order with (2048) / without (4096) the non-temporal policy (A/B: no difference). */
 /* which form the LAST streaming decode launch of this thread took: 0 = one block per CU, 1 = fine grid, 2 = two-pass resident rows (harness builds) */
 int bd_last_decode_form(void);
+/* What the library decided about the LAST streaming decode launch (gemv_stream_kernel: the decode Linears, bd_tenant_linear) of this thread: copies
+ * up to n of the BD_DECODE_PLAN_INTS values below into out and returns BD_DECODE_PLAN_INTS.
+ *   [0] the launch's return code (a refused launch records the fields decided until then)
+ *   [1..12] the kernel's template parameters DT, NM, HASW, NS, NW, WNAT, AUX, PK, XL, EPI, WT, FG   (bd_gemv_stream.h)
+ *   [13] [14] grid x, y   [15] threads per block   [16] dynamic LDS bytes   [17] columns per block   [18] [19] LDS offset and stride of the
+ *   resident activation rows   [20] bd_last_decode_form() */
+#define BD_DECODE_PLAN_INTS 21
+int bd_last_decode_plan(int32_t* out, int n);
+/* 1 = the streaming decode launches of this thread are DRY RUNS: decided, recorded (bd_last_decode_plan) and answered with the code the launch
+ * would return, without any call to the device -- the pointers are never dereferenced.  Every other kernel still launches. */
+int bd_set_decode_dry_run(int on);
 /* which decode_attn_kernel instantiation the LAST bd_srv_decode_attention launch of this thread ran: nsplit | DEPTH << 8 | MAXS << 16 | G << 24
  * (nsplit = key-range splits, 1 = the unsplit launch; DEPTH = K / V row ring, 2 or 4; MAXS = splits the in-launch merge is written for, 4 or 16;
  * G = query heads per kv head).  0 before the first launch. */
