@@ -65,6 +65,7 @@ SIGNATURES = {
     "bd_binarize": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _i64, _vp]),
     "bd_binarize_workspace_bytes": (_i64, [_i64, _i64]),
     "bd_merge_delta": (_ci, [_vp, _i64, _vp, _vp, _i64, _i64, _ci, _vp]),
+    "bd_tenant_signs_load": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _ci, _ci, _i64, _i64, _i64, _vp]),
     "bd_set_gemm_variant": (_ci, [_ci]),
     "bd_last_gemm_variant": (_ci, []),
     "bd_set_tile_group_m": (_ci, [_ci]),

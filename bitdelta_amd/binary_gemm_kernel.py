@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import DTYPE_CODE, WORD_DTYPE, check, lib, ptr, require_gpu, stream_ptr, workspace
 
 __all__ = ["pack", "unpack", "binary_matmul", "binary_bmm", "delta_bmm", "binary_linear", "binary_linear_residual_norm", "tenant_linear", "tile_masks",
-           "pack_decode_masks", "binary_linear_decode", "decode_shape_ok"]
+           "pack_decode_masks", "load_decode_masks", "binary_linear_decode", "decode_shape_ok"]
 
 
 def pack(x, n_bits=32):
@@ -268,6 +268,33 @@ def pack_decode_masks(mask):
     if tp != T:
         out = torch.nn.functional.pad(out, (0, tp - T))
     return out.contiguous()
+
+
+def load_decode_masks(src, *, mask=None, packed=None, slot=0, col_off=0, col_blk=None, col_stride=0):
+    """Write ONE tenant's sign words of one projection, src [K/32, N_src] int32 (reference / diff.pt layout; rows may be strided), IN PLACE into
+    packed : slot `slot` of a whole tenant set's pack_decode_masks(...) result, [ceil(Nf/16), ceil(KW/4), 4, 16, t_pad], and / or
+    mask   : the tenant's plane [K/32, Nf] of the fused reference-layout words (rows may be strided),
+    at the fused column n' = col_off + (n // col_blk) * col_stride + n % col_blk (col_blk=None: N_src, a plain offset).  One launch of
+    bd_tenant_signs_load; the other slots, the padding slots and the padding columns keep their bytes.  Nothing is allocated or returned."""
+    require_gpu(src, mask, packed)
+    assert src.dim() == 2 and src.dtype == torch.int32 and (src.stride(1) == 1 or src.shape[1] <= 1)
+    assert mask is not None or packed is not None, "no destination"
+    KW, N_src = src.shape
+    n_fused, t_pad = None, 1
+    ld = lambda m: m.stride(0) if m.shape[0] > 1 else max(m.stride(0), m.shape[1])      # (the stride of a one-row tensor says nothing)
+    if mask is not None:
+        assert mask.dim() == 2 and mask.dtype == torch.int32 and mask.shape[0] == KW and (mask.stride(1) == 1 or mask.shape[1] <= 1)
+        n_fused = mask.shape[1]
+    if packed is not None:
+        assert packed.dim() == 5 and packed.dtype == torch.int32 and packed.is_contiguous() and packed.shape[1:4] == ((KW + 3) // 4, 4, 16)
+        t_pad = packed.shape[4]
+        if n_fused is None:
+            n_fused = packed.shape[0] * 16
+        assert packed.shape[0] == (n_fused + 15) // 16
+    with torch.cuda.device(src.device):
+        check(lib().bd_tenant_signs_load(ptr(src), ld(src), KW, N_src, ptr(mask), ld(mask) if mask is not None else 0, ptr(packed), n_fused,
+                                         t_pad, int(slot) if packed is not None else 0, int(col_off), int(max(N_src, 1) if col_blk is None else col_blk), int(col_stride),
+                                         stream_ptr()), "load_decode_masks")
 
 
 def decode_shape_ok(B, M, N, K, n_masks, layout="packed"):

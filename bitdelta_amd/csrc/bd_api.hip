@@ -142,6 +142,35 @@ extern "C" int bd_unpack(const void* words, int64_t batch, int64_t KW, int64_t N
     return launch_status();
 }
 
+// ------------------------------------------------------------------ one tenant's sign words into the decode / prefill buffers
+extern "C" int bd_tenant_signs_load(const int32_t* src, int64_t ld_src, int64_t KW, int64_t N_src, int32_t* mask_dst, int64_t ld_mask_dst,
+                                    int32_t* packed_dst, int64_t N_fused, int t_pad, int slot, int64_t col_off, int64_t col_blk,
+                                    int64_t col_stride, void* stream) {
+    if (KW < 0 || N_src < 0 || N_fused < 0 || KW > (1LL << 26) || N_src > (1LL << 30) || N_fused > (1LL << 30)) return BD_E_BAD_SHAPE;
+    if (t_pad != 1 && t_pad != 2 && t_pad != 4 && t_pad != 6 && t_pad != 8 && t_pad != 12 && t_pad != 16) return BD_E_BAD_SHAPE;
+    if (slot < 0 || slot >= t_pad) return BD_E_BAD_SHAPE;
+    if (col_blk < 1 || N_src % col_blk) return BD_E_BAD_GROUPS;
+    const int64_t nblk = N_src / col_blk;
+    if (col_off < 0 || col_off > N_fused || (nblk > 1 && (col_stride < col_blk || col_stride > N_fused))) return BD_E_BAD_SHAPE;
+    if (N_src > 0 && col_off + (nblk - 1) * (nblk > 1 ? col_stride : 0) + col_blk > N_fused) return BD_E_BAD_SHAPE;
+    if (ld_src < N_src || (mask_dst && ld_mask_dst < N_fused)) return BD_E_BAD_SHAPE;
+    if (N_src == 0 || KW == 0) return BD_OK;
+    if (!src || (!mask_dst && !packed_dst)) return BD_E_NULL;
+    const int64_t NIT = (KW + 3) / 4;
+    const unsigned gx = (unsigned)((N_src + 255) / 256);
+    const int64_t gy = (NIT + 3) / 4;              // a block = 256 source columns x 4 `it` (one per wave)
+    if (gy > 65535) return BD_E_BAD_SHAPE;
+    const bool adjacent = col_blk % 4 == 0 && col_off % 4 == 0 && (nblk == 1 || col_stride % 4 == 0);
+    int vec = 0;
+    if (((uintptr_t)src & 15) == 0 && ld_src % 4 == 0) vec |= 1;
+    if (adjacent && mask_dst && ((uintptr_t)mask_dst & 15) == 0 && ld_mask_dst % 4 == 0) vec |= 2;
+    if (adjacent && packed_dst && t_pad == 1 && ((uintptr_t)packed_dst & 15) == 0) vec |= 4;
+    hipLaunchKernelGGL(tenant_signs_load_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)src,
+                       (long long)ld_src, (int)KW, (int)N_src, (uint32_t*)mask_dst, (long long)ld_mask_dst, (uint32_t*)packed_dst, t_pad, slot,
+                       (int)col_off, (int)col_blk, (int)(nblk > 1 ? col_stride : 0), vec);
+    return launch_status();
+}
+
 // ------------------------------------------------------------------ GEMM dispatch
 namespace {
 

@@ -198,4 +198,109 @@ __global__ void __launch_bounds__(256) merge_kernel(unsigned short* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// tenant_signs_load: ONE tenant's sign words of ONE projection, src[KW][N_src] (reference / diff.pt layout, row stride ld_src), into
+//   packed : slot `slot` of the streaming decode kernel's packed words  P'[ceil(Nf/16)][NIT = ceil(KW/4)][4 g][16 c][t_pad]  -- the dword at
+//            [tile][it][g][c][slot] has byte s = byte g of src[4 it + s][n], rows >= KW reading as zero (binary_gemm_kernel.pack_decode_masks);
+//   mask   : the tenant's plane of the fused reference-layout words, mask[KW][Nf] (row stride ld_mask), the same words unshuffled
+// at the fused column  n' = col_off + (n / col_blk) * col_stride + n % col_blk  (16 tile + c = n').  Either destination may be null.  Only the
+// dwords of this slot and of this projection's columns are stored: the other tenants, the padding slots and the padding columns keep their bytes.
+// Lane = 4 source columns x the 4 word rows of one `it`: four 16-byte non-temporal loads (a wave reads 1 KiB per row), a 4 x 4 byte transpose
+// with v_perm, 16 packed dwords.  A block = 256 source columns (16 tiles when the map keeps them together) x 4 consecutive `it`, one per
+// wave: the single-dword stores at stride 4 t_pad bytes that fill one tile's lines are issued close together.
+// t_pad == 1 (and a map that keeps a lane's 4 columns adjacent and aligned): the 4 columns of one g are one 16-byte store.
+__device__ __forceinline__ void transpose4x4_bytes(const uint32_t a[4], uint32_t d[4]) {
+    // d[g] byte s = a[s] byte g.  v_perm selector bytes: 0..3 = bytes of the SECOND operand, 4..7 = bytes of the first
+    const uint32_t t0 = __builtin_amdgcn_perm(a[1], a[0], 0x05010400u), t1 = __builtin_amdgcn_perm(a[1], a[0], 0x07030602u);
+    const uint32_t u0 = __builtin_amdgcn_perm(a[3], a[2], 0x05010400u), u1 = __builtin_amdgcn_perm(a[3], a[2], 0x07030602u);
+    d[0] = __builtin_amdgcn_perm(u0, t0, 0x05040100u);
+    d[1] = __builtin_amdgcn_perm(u0, t0, 0x07060302u);
+    d[2] = __builtin_amdgcn_perm(u1, t1, 0x05040100u);
+    d[3] = __builtin_amdgcn_perm(u1, t1, 0x07060302u);
+}
+
+__global__ void __launch_bounds__(256) tenant_signs_load_kernel(const uint32_t* __restrict__ src, long long ld_src, int KW, int N_src,
+                                                                uint32_t* __restrict__ mask, long long ld_mask,
+                                                                uint32_t* __restrict__ packed, int t_pad, int slot, int col_off, int col_blk,
+                                                                int col_stride, int vec) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n0 = (blockIdx.x * 64 + lane) * 4;
+    if (n0 >= N_src) return;
+    const int NIT = (KW + 3) >> 2;
+    const int cnt = min(4, N_src - n0);
+    // fused column of each of the lane's source columns
+    int nf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + (j < cnt ? j : 0);
+        nf[j] = col_off + (n / col_blk) * col_stride + n % col_blk;
+    }
+    // vec bit 0: 16-byte source loads are aligned; bit 1: ... mask stores; bit 2: ... packed stores (t_pad == 1).  Host-checked pointer / stride /
+    // map alignment; the lane adds "all 4 columns exist" (they are then adjacent in the fused order too: col_blk % 4 == 0 is part of the bits)
+    const bool full = cnt == 4;
+    const int it = blockIdx.y * 4 + wave;
+    if (it >= NIT) return;
+    {
+        uint32_t w[4][4];                       // [s][j]
+        if (full && (vec & 1) && 4 * it + 3 < KW) {        // the common case: the four loads issue back to back
+            const uint32_t* p = src + (long long)(4 * it) * ld_src + n0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const u32x4_t v = __builtin_nontemporal_load((const u32x4_t*)(p + s * ld_src));
+                w[s][0] = v.x; w[s][1] = v.y; w[s][2] = v.z; w[s][3] = v.w;
+            }
+        } else {                                           // ragged edges: rows past KW read as zero, columns one by one
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int row = 4 * it + s;
+                const uint32_t* p = src + (long long)row * ld_src + n0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) w[s][j] = (row < KW && j < cnt) ? __builtin_nontemporal_load(p + j) : 0u;
+            }
+        }
+        if (mask) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int row = 4 * it + s;
+                if (row >= KW) continue;
+                uint32_t* q = mask + (long long)row * ld_mask;
+                if (full && (vec & 2)) {
+                    u32x4_t v;
+                    v.x = w[s][0]; v.y = w[s][1]; v.z = w[s][2]; v.w = w[s][3];
+                    *(u32x4_t*)(q + nf[0]) = v;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (j < cnt) q[nf[j]] = w[s][j];
+                }
+            }
+        }
+        if (packed) {
+            uint32_t d[4][4];                   // [j][g]
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t a[4] = {w[0][j], w[1][j], w[2][j], w[3][j]};
+                transpose4x4_bytes(a, d[j]);
+            }
+            if (full && (vec & 4)) {            // t_pad == 1: [tile][it][g][16 c], the lane's 4 columns are c .. c + 3 of one tile
+                uint32_t* q = packed + (((long long)(nf[0] >> 4) * NIT + it) * 4) * 16 + (nf[0] & 15);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    u32x4_t v;
+                    v.x = d[0][g]; v.y = d[1][g]; v.z = d[2][g]; v.w = d[3][g];
+                    *(u32x4_t*)(q + g * 16) = v;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j >= cnt) continue;
+                    uint32_t* q = packed + ((((long long)(nf[j] >> 4) * NIT + it) * 4) * 16 + (nf[j] & 15)) * t_pad + slot;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) q[(long long)g * 16 * t_pad] = d[j][g];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace bd

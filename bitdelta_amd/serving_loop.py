@@ -18,13 +18,15 @@ running the reference's modules under HF, all of them launch-count / traffic onl
     is captured once as a hipGraph and replayed: greedy feedback happens on the device, the host only polls the stop flags.
 """
 import math
+import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .binary_gemm_kernel import (binary_linear, binary_linear_residual_norm, binary_linear_swiglu, binary_linear_decode, decode_shape_ok, fused_norm_ok, handoff_ok,
-                                 pack_decode_masks, tenant_linear, tile_weight)
+                                 load_decode_masks, pack_decode_masks, tenant_linear, tile_weight)
+from ._lib import require_gpu
 from .quant import (cat_gptq4, dequantize_base_gptq4, dequantize_base_int8, pack_gptq4_params, quantize_base_gptq4, quantize_base_int8,
                     tile_weight_gptq4, tile_weight_int8, weight_scale)
 from .diff import binarize
@@ -57,6 +59,51 @@ def handoff_norm(nw):
     m = float(nw.detach().abs().max())
     s = 1.0 if not math.isfinite(m) or m <= 0.0 else 2.0 ** math.ceil(math.log2(m))
     return (nw.float() / s).to(nw.dtype), s
+
+
+def _pow2_scale(m):
+    """handoff_norm's s for a largest |norm weight| of m"""
+    return 1.0 if not math.isfinite(m) or m <= 0.0 else 2.0 ** math.ceil(math.log2(m))
+
+
+def fused_columns(widths, interleave8):
+    """Where the output columns of several projections sit in a FusedDeltaLinear -- the ONE definition, used by __init__ (which permutes whole
+    tensors, through fused_perm) and by load_tenant (which writes one tenant's columns).  A few integers, no tensor.  Returns (gsz, maps):
+    gsz   columns per alpha group;
+    maps  one (col_off, col_blk, col_stride) per projection: its column n is stored at col_off + (n // col_blk) * col_stride + n % col_blk."""
+    widths = [int(n) for n in widths]
+    if interleave8:
+        assert len(widths) == 2 and widths[0] == widths[1] and widths[0] % 8 == 0
+        return 8, [(0, 8, 16), (8, 8, 16)]
+    gsz, maps, off = 0, [], 0
+    for n in widths:
+        gsz = math.gcd(gsz, n)
+        maps.append((off, n, 0))
+        off += n
+    return gsz, maps
+
+
+def fused_perm(widths, interleave8, device=None):
+    """fused_columns' maps as an index tensor: stored row -> row of the plain concatenation; None where that is the identity"""
+    if not interleave8:
+        return None
+    perm = torch.empty(sum(widths), dtype=torch.long, device=device)
+    first = 0
+    for n_i, (off, blk, stride) in zip(widths, fused_columns(widths, True)[1]):
+        n = torch.arange(n_i, device=device)
+        perm[off + (n // blk) * stride + n % blk] = first + n
+        first += n_i
+    return perm
+
+
+def fused_alpha(coeffs, widths, interleave8):
+    """alpha [T, G] (one scale per group of fused_columns' gsz stored columns) and alpha_pair [T, 2] (interleaved pairs; else None) from one
+    tensor of T coeffs per projection.  With T = 1 it is one tenant's row of both."""
+    if interleave8:
+        pair = torch.stack([c.float().reshape(-1) for c in coeffs], 1)                          # [T, 2] (gate, up)
+        return pair.repeat(1, widths[0] // 8), pair                                              # [T, N/8]: g, u, g, u, ...
+    gsz = fused_columns(widths, False)[0]
+    return torch.cat([c.float().reshape(-1, 1).expand(-1, n // gsz) for c, n in zip(coeffs, widths)], 1), None
 
 
 def padded_length(longest):
@@ -102,20 +149,13 @@ class FusedDeltaLinear(nn.Module):
         self.widths = widths
         self.interleave8 = bool(interleave8)
         weight, mask = torch.cat(weights, 0), torch.cat(masks, 2)                               # [N, K], [T, K/32, N]
-        if self.interleave8:
-            assert len(widths) == 2 and widths[0] == widths[1] and widths[0] % 8 == 0
-            inter = widths[0]
-            perm = torch.arange(2 * inter, device=weight.device).view(2, inter // 8, 8).transpose(0, 1).reshape(-1)
+        perm = fused_perm(widths, self.interleave8, weight.device)
+        if perm is not None:
             weight, mask = weight[perm], mask[:, :, perm]
-            gsz = 8
-            alpha = torch.stack([c.float().reshape(-1) for c in coeffs], 1)                     # [T, 2] (gate, up)
-            self.register_buffer("alpha_pair", alpha.contiguous())
-            alpha = alpha.repeat(1, inter // 8)                                                  # [T, N/8]: g, u, g, u, ...
+        alpha, pair = fused_alpha(coeffs, widths, self.interleave8)
+        if pair is not None:
+            self.register_buffer("alpha_pair", pair.contiguous())
         else:
-            gsz = 0
-            for n in widths:
-                gsz = math.gcd(gsz, n)
-            alpha = torch.cat([c.float().reshape(-1, 1).expand(-1, n // gsz) for c, n in zip(coeffs, widths)], 1)
             self.alpha_pair = None
         cb = None
         if self.base_int8:
@@ -259,6 +299,54 @@ class FusedDeltaLinear(nn.Module):
         v.wscale = v.group_params = v.mask_packed = v.weight_tiled = None
         return v
 
+    def check_tenant(self, t, masks, coeffs):
+        """load_tenant's refusals, without touching anything: raises ValueError / IndexError; returns the coeffs as one-element fp32 tensors"""
+        T, KW, _ = self.mask.shape
+        if not (isinstance(t, int) and 0 <= t < T):
+            raise IndexError("tenant %r: this Linear holds slots 0 .. %d" % (t, T - 1))
+        if len(masks) != len(self.widths) or len(coeffs) != len(self.widths):
+            raise ValueError("one mask and one coeff per projection: %d expected" % len(self.widths))
+        out = []
+        for m, c, n in zip(masks, coeffs, self.widths):
+            if not torch.is_tensor(m) or m.dtype != torch.int32:
+                raise ValueError("sign words are int32 tensors")
+            if tuple(m.shape) != (KW, n):
+                raise ValueError("sign words of shape %s where the module was built with %s" % (tuple(m.shape), (KW, n)))
+            if m.device != self.mask.device:
+                raise ValueError("sign words on %s, the module on %s" % (m.device, self.mask.device))
+            c = torch.as_tensor(c)
+            if c.numel() != 1 or not (c.is_floating_point()):
+                raise ValueError("one floating-point coeff per projection")
+            out.append(c.detach().reshape(1))
+        return out
+
+    @torch.no_grad()
+    def load_tenant(self, t, masks, coeffs):
+        """Replace slot t's fine-tune IN PLACE: one [K/32, N_i] int32 mask and one scalar coeff per projection, the widths the module was built
+        with.  One launch of the sign-load kernel per projection writes tenant t's plane of `mask` and slot t of `mask_packed` (where the module
+        keeps decode copies); alpha[t] / alpha_pair[t] follow __init__'s rule (fused_alpha).  No buffer is reallocated -- every data_ptr stays,
+        so captured graphs stay valid -- and the base (16-bit, int8 or GPTQ) is not touched."""
+        coeffs = self.check_tenant(t, masks, coeffs)
+        require_gpu(self.mask, *masks)
+        maps = fused_columns(self.widths, self.interleave8)[1]
+        for m, (off, blk, stride) in zip(masks, maps):
+            load_decode_masks(m if m.stride(1) == 1 else m.contiguous(), mask=self.mask[t], packed=self.mask_packed, slot=t, col_off=off,
+                              col_blk=blk, col_stride=stride)
+        alpha, pair = fused_alpha([c.to(self.alpha.device) for c in coeffs], self.widths, self.interleave8)
+        self.alpha[t].copy_(alpha[0])
+        if pair is not None:
+            self.alpha_pair[t].copy_(pair[0])
+
+    def tenant_signs(self, t):
+        """(masks, coeffs) of slot t, un-fused: what load_tenant takes.  Concatenated projections are views of `mask`, an interleaved pair
+        is de-interleaved into copies; the coeffs are views of alpha / alpha_pair."""
+        m = self.mask[t]
+        if self.interleave8:
+            v = m.view(m.shape[0], self.widths[0] // 8, 2, 8)
+            return [v[:, :, i, :].reshape(m.shape[0], -1) for i in range(2)], [self.alpha_pair[t, i] for i in range(2)]
+        gsz, maps = fused_columns(self.widths, False)
+        return [m[:, off:off + n] for (off, n, _) in maps], [self.alpha[t, off // gsz] for (off, _, _) in maps]
+
     def split(self, y):
         """per-projection outputs of y = forward(x)  (undoes the interleaved row order)"""
         if self.interleave8:
@@ -336,6 +424,7 @@ class TenantDecoder(nn.Module):
         self._kv_cache = None           # ONE KV cache per decoder, shared by every slot
         self._capture_stream = None
         self._tenant_views = {}         # tenant -> one-tenant view of this decoder (tenant_view)
+        self._sessions = weakref.WeakSet()   # live TenantSessions: load_tenant drops their captured graphs when a hand-off scale changes
         self.fuse_qkv_norm = False      # RMSNorm folded into the q|k|v launch
         # RMSNorm folded into the gate|up launch (SwiGLU stays in its epilogue either way): every block re-normalises all rows (rows + norm
         # weights from L2) to save one ~4.5 us launch.  Same-process A/Bs at the end of round 4, with the resident-row form (which needs no
@@ -447,9 +536,118 @@ class TenantDecoder(nn.Module):
         key = "_hn_" + which
         v = getattr(layer, key, None)
         if v is None:
+            # s is read on the host and baked into captured launches (ssq_scale, eps / s^2): it is made in the warm-up step, never inside a capture
+            assert not torch.cuda.is_current_stream_capturing(), "the hand-off norm cache is computed outside graph capture"
             v = handoff_norm(getattr(layer, which))
             setattr(layer, key, v)
         return v
+
+    # ---------------------------------------------------------------- swapping one slot's fine-tune
+    _DENSE = ("embed", "final_norm", "lm_head")
+    _LINEARS = ("qkv", "o", "gate_up", "down")
+
+    def tenant_state(self, t):
+        """Slot t's fine-tune as load_tenant takes it: {"layers": [{"qkv" | "o" | "gate_up" | "down": (masks, coeffs), "norm1", "norm2"}, ...],
+        "embed", "final_norm", "lm_head"} -- un-fused, de-interleaved sign words and coeffs per projection, the dense rows.  Views of this decoder's
+        storage where the layout allows (copies for interleaved pairs): clone it to keep it across a later load into the same slot."""
+        assert 0 <= t < self.T
+        layers = []
+        for layer in self.layers:
+            d = {name: getattr(layer, name).tenant_signs(t) for name in self._LINEARS}
+            d["norm1"], d["norm2"] = layer.norm1[t], layer.norm2[t]
+            layers.append(d)
+        return {"layers": layers, "embed": self.embed[t], "final_norm": self.final_norm[t], "lm_head": self.lm_head[t]}
+
+    def _check_state(self, t, state):
+        if not (isinstance(t, int) and 0 <= t < self.T):
+            raise IndexError("tenant %r: this decoder holds slots 0 .. %d" % (t, self.T - 1))
+        if len(state["layers"]) != len(self.layers):
+            raise ValueError("%d layers in the state, %d in the decoder" % (len(state["layers"]), len(self.layers)))
+        rows = [(getattr(self, n), state[n], n) for n in self._DENSE]
+        for layer, d in zip(self.layers, state["layers"]):
+            rows += [(layer.norm1, d["norm1"], "norm1"), (layer.norm2, d["norm2"], "norm2")]
+            for name in self._LINEARS:
+                getattr(layer, name).check_tenant(t, *d[name])
+        for dst, src, name in rows:
+            if dst.stride(0) == 0 and dst.shape[0] > 1:
+                raise ValueError("%s is one row expanded over the tenants (shared_heads=True): a slot cannot be written alone" % name)
+            if tuple(src.shape) != tuple(dst.shape[1:]) or src.dtype != dst.dtype:
+                raise ValueError("%s: %s %s where the decoder holds %s %s" % (name, tuple(src.shape), src.dtype, tuple(dst.shape[1:]), dst.dtype))
+
+    def _hn_peaks(self, t, state):
+        """Host values the s rule needs, for every cached hand-off norm at once: {(layer index, which): max |new row t|}, and each entry's
+        per-tenant maxima `_hnpeak_*` (kept on the host from then on).  ONE device reduction chain and ONE transfer per load, however many
+        entries are cached; no transfer at all when nothing is cached, or when the maxima are known and the new rows are host tensors."""
+        keys, parts, fresh = [], [], []
+        for li, (layer, d) in enumerate(zip(self.layers, state["layers"])):
+            for which in ("norm1", "norm2"):
+                if getattr(layer, "_hn_" + which, None) is not None:
+                    keys.append((li, which))
+                    parts.append(d[which].detach().abs().max().reshape(1).float())
+        for li, which in keys:
+            if getattr(self.layers[li], "_hnpeak_" + which, None) is None:
+                fresh.append((li, which))
+                parts.append(getattr(self.layers[li], which).detach().abs().amax(dim=1).float())
+        if not keys:
+            return {}
+        if any(p.is_cuda for p in parts):
+            parts = [p.to(self.dev) for p in parts]
+        host = torch.cat(parts).tolist()
+        for i, (li, which) in enumerate(fresh):
+            lo = len(keys) + i * self.T
+            setattr(self.layers[li], "_hnpeak_" + which, host[lo:lo + self.T])
+        return dict(zip(keys, host[:len(keys)]))
+
+    def _reload_hn(self, layer, which, t, peak):
+        """a cached hand-off norm (nw / s, s) after row t of the norm changed (peak = max |new row|, a host float): the row is rewritten in place
+        while the power of two s over the new tenant set is the old one; otherwise the entry is rebuilt.  Returns True when s changed
+        (captured launches baked the old one)."""
+        v = getattr(layer, "_hn_" + which)
+        nw = getattr(layer, which)
+        peaks = getattr(layer, "_hnpeak_" + which)
+        peaks[t] = peak
+        m = max(peaks) if all(math.isfinite(p) for p in peaks) else float("nan")
+        s = _pow2_scale(m)
+        if s == v[1]:
+            v[0][t].copy_((nw[t].float() / s).to(nw.dtype))
+            return False
+        setattr(layer, "_hn_" + which, ((nw.float() / s).to(nw.dtype), s))
+        return True
+
+    @torch.no_grad()
+    def load_tenant(self, t, state):
+        """Replace the fine-tune in slot t IN PLACE (state: see tenant_state): every delta Linear's sign words and scales through
+        FusedDeltaLinear.load_tenant, the tenant's rows of the norms, the embedding and the lm_head by copies on the current stream.  Storage and
+        pointers stay, so captured decode steps stay valid and the other tenants' rows are not touched.  The one thing a captured step bakes that
+        depends on the whole tenant set is the hand-off norm's power-of-two scale s (handoff_norm): where a cached entry's s is still right
+        the cached row is rewritten in place; where it moved, the entry is rebuilt and every captured graph of this decoder and of its live
+        sessions is dropped (the next step captures again).  Host synchronisation: at most ONE device-to-host read per load -- the maxima of
+        the new norm rows of every cached entry, reduced on the device and read back together (_hn_peaks); none when no hand-off norm is cached
+        yet, or when the state's norm rows are host tensors.  That read waits for work already queued on the stream.  Refuses a decoder whose per-tenant tensors are one row expanded (shared_heads).
+        The caller makes sure slot t is not generating (TenantSession.load_tenant checks)."""
+        self._check_state(t, state)
+        require_gpu(self.embed)
+        assert not torch.cuda.is_current_stream_capturing(), "a load reads the hand-off scale on the host: not inside a graph capture"
+        peaks = self._hn_peaks(t, state)                   # the load's one host read (none without a cached hand-off norm)
+        rescaled = False
+        for li, (layer, d) in enumerate(zip(self.layers, state["layers"])):
+            for name in self._LINEARS:
+                getattr(layer, name).load_tenant(t, *d[name])
+            for which in ("norm1", "norm2"):
+                getattr(layer, which)[t].copy_(d[which])
+                if (li, which) in peaks:
+                    rescaled |= self._reload_hn(layer, which, t, peaks[(li, which)])
+        for name in self._DENSE:
+            getattr(self, name)[t].copy_(state[name])
+        # The decoder's own one-tenant view is dropped and rebuilt on its next use.  That is enough: a view slices this storage and caches nothing
+        # derived from tenant data (it only prefills, where no hand-off norm is made), so a view a caller still holds reads the new fine-tune too.
+        self._tenant_views.pop(t, None)
+        if rescaled:
+            for slot in self._static.values():
+                slot["graph"] = None
+            for sess in list(self._sessions):
+                sess._graphs.clear()
+        return rescaled
 
     def _layer(self, layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid=False, next_layer=None, h_in=None, ragged=None):
         """one decoder layer; returns (x, ssq_valid): whether self._ssq / self._xw hold the partial sums of squares of the returned x and its
@@ -798,8 +996,26 @@ class TenantSession:
         self.stop_ids = torch.full((T, max(int(max_stop_ids), 1)), -1, dtype=torch.long, device=dev)
         self.out = torch.zeros(T, dec.max_len, dtype=torch.long, device=dev)      # (a caller may swap in a strided view BEFORE the first step)
         self._graphs = {}
+        dec._sessions.add(self)
 
     # ------------------------------------------------------------ admission
+    @torch.no_grad()
+    def load_tenant(self, t, state):
+        """Put another fine-tune into slot t (TenantDecoder.load_tenant) while the other tenants keep generating: refused (RuntimeError) while
+        tenant t is active.  Runs on the current stream, i.e. ordered between the replays around it; tenant t's validity bytes, stop reason, token
+        count and output row are cleared, nobody else's state, cache rows or validity bytes are touched.  Host reads: tenant t's own activity
+        flag (as in submit) and, where a hand-off norm is cached, the decoder's one read of the new norm rows' maxima."""
+        if not (isinstance(t, int) and 0 <= t < self.T):
+            raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
+        if bool(self.active_flags[t]):
+            raise RuntimeError("tenant %d is still generating" % t)
+        rescaled = self.dec.load_tenant(t, state)
+        self.cache["valid"][t].zero_()
+        self.done[t] = 0
+        self.n[t] = 0
+        self.out[t].zero_()
+        return rescaled
+
     def _stops(self, stop_token_ids):
         s_ = sorted(int(i) for i in (stop_token_ids or ()))
         if len(s_) > self.stop_ids.shape[1]:

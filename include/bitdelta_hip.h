@@ -337,6 +337,25 @@ int64_t bd_binarize_workspace_bytes(int64_t N, int64_t K);
 int bd_merge_delta(void* W, int64_t ldw, const int32_t* P, const float* coeff, int64_t N, int64_t K, int dtype,
                    void* stream);
 
+/* Replace ONE tenant's sign words of ONE projection inside the buffers of a fused multi-tenant Linear, in place.
+ *   src         [KW][N_src] int32, the reference / diff.pt layout: row stride ld_src elements (>= N_src), columns contiguous.
+ *   packed_dst  the packed decode words of the whole tenant set, int32 [ceil(N_fused/16)][ceil(KW/4)][4 g][16 c][t_pad] (what
+ *               bd_binary_linear_decode reads with packed = 1): the dword at [tile][it][g][c][slot] gets byte s = byte g of
+ *               src[4 it + s][n], rows >= KW reading as zero.  Only the dwords of `slot` and of this projection's columns are
+ *               written: the other slots, the padding slots and the columns between N_fused and 16 ceil(N_fused/16) keep their bytes.
+ *   mask_dst    the tenant's plane of the fused reference-layout words, [KW][N_fused] with row stride ld_mask_dst (>= N_fused): the
+ *               same words, unshuffled (what prefill reads).
+ *   Either destination may be NULL (skipped); both NULL is BD_E_NULL.
+ * Column map, source column n -> fused column n' (16 tile + c = n'):   n' = col_off + (n / col_blk) * col_stride + n % col_blk
+ *   concatenated projections:          col_off = the projection's first column, col_blk = N_src (col_stride unused)
+ *   a pair interleaved in blocks of 8: col_off = 8 * (0 | 1), col_blk = 8, col_stride = 16
+ * t_pad in {1, 2, 4, 6, 8, 12, 16} and 0 <= slot < t_pad, else BD_E_BAD_SHAPE; col_blk >= 1 dividing N_src, else BD_E_BAD_GROUPS; every
+ * mapped column inside N_fused, blocks that do not overlap (col_stride >= col_blk) and ld_src >= N_src, else BD_E_BAD_SHAPE.  All of it
+ * is checked before any device work; N_src == 0 or KW == 0 is a no-op.  No workspace, no atomics: one launch on `stream`. */
+int bd_tenant_signs_load(const int32_t* src, int64_t ld_src, int64_t KW, int64_t N_src, int32_t* mask_dst, int64_t ld_mask_dst,
+                         int32_t* packed_dst, int64_t N_fused, int t_pad, int slot, int64_t col_off, int64_t col_blk,
+                         int64_t col_stride, void* stream);
+
 /* The tuning / A-B hooks (bd_set_*, bd_last_*) are declared in bitdelta_hip_test.h: thread-local, not part of the stable interface a
  * reference-side binding needs (INTEGRATION.md binds none of them), free to change between versions. */
 
