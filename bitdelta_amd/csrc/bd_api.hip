@@ -2062,3 +2062,33 @@ extern "C" int bd_merge_delta(void* W, int64_t ldw, const int32_t* P, const floa
                            (int)N, (int)K, (long long)ldw);
     return launch_status();
 }
+
+// (last in the file: the kernels of a code object lie in the order the host code asks for them, and the decode step is sensitive to where
+// its kernels lie -- profiles/decode_dispatch_refactor.txt; a new entry goes behind every kernel that exists)
+extern "C" int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim,
+                                               int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb,
+                                               int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int dtype,
+                                               void* stream) {
+    // every check below is host arithmetic: nothing touches the device before the geometry is known to be the kernel's
+    if (B < 0 || H < 1 || KVH < 1 || H % KVH || Sq < 1 || q0 < 0 || Lc < 1 || (int64_t)q0 + Sq > Lc) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (B == 0) return BD_OK;
+    if (!Q || !Kc || !Vc || !O) return BD_E_NULL;
+    if (head_dim != 128 || (sqb | sqs | skb | skh | sks | svb | svh | svs | sob | sos) % 8 || !aligned16(Q) || !aligned16(Kc) || !aligned16(Vc) ||
+        !aligned16(O) || (int64_t)B * H * ((Sq + 127) / 128) > 0x7fffffffLL)
+        return BD_E_BAD_SHAPE;
+    PrefillAttnCachedParams p;
+    p.q = (const unsigned short*)Q; p.k = (const unsigned short*)Kc; p.v = (const unsigned short*)Vc; p.o = (unsigned short*)O;
+    p.sqb = sqb; p.sqs = sqs; p.skb = skb; p.skh = skh; p.sks = sks; p.svb = svb; p.svh = svh; p.svs = svs; p.sob = sob; p.sos = sos;
+    p.kv_start = kv_start; p.B = B; p.Sq = Sq; p.H = H; p.KVH = KVH; p.nqb = (Sq + 127) / 128; p.q0 = q0; p.Lc = Lc;
+    p.c = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(p.nqb * H * B));
+    static std::atomic<uint64_t> lds_done[2];               // the kernel needs more than the default dynamic LDS limit
+    const int di = dtype == BD_BF16 ? 1 : 0;
+    const void* fn = di ? (const void*)prefill_attn_kernel<DT_BF16, true> : (const void*)prefill_attn_kernel<DT_F16, true>;
+    if (!ensure_dyn_lds(fn, PREFILL_ATTN_LDS, lds_done[di])) return BD_E_LAUNCH;
+    if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    return launch_status();
+}

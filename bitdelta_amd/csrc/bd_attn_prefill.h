@@ -36,8 +36,35 @@ struct PrefillAttnParams {
     int causal;
 };
 
-template <int DT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(const PrefillAttnParams p) {
+// The CACHED form (prefill_attn_kernel<DT, true>): a chunk of Sq queries at absolute positions q0 .. q0 + Sq - 1 over the keys kv_start[b] .. q0 + row
+// of the KV caches [B, KVH, Lc, 128] -- the second turn of a conversation, or one chunk of a long prompt, after rope_kv_append has written the
+// chunk's own rows.  Always causal.  The tile walk is the one above (64-key tiles at absolute multiples of 64 from kv_start / 64, the same two MFMA
+// products, online softmax and epilogue); what moves is a query's absolute position q0 + row in the causal tests and the per-wave tile skip, the
+// tile range (j_hi = (q0 + last row) / 64), and the K / V addressing (head and key strides).  A query is one MFMA column and a fully masked tile
+// leaves a row's state as it was (alpha = exp2(0) = 1, p = 0), so a row's output is bit for bit the whole-prompt kernel's output for that row.
+// Cache rows at or past q0 + Sq are never trusted: a staged tile may reach past the last written row (and past Lc when Lc % 64 != 0), so key
+// addresses are clamped into the allocation, the causal mask overwrites such a key's score, and its V row is zeroed on the way into LDS (0 * NaN
+// inside the PV MFMA would reach every query of the wave).  Lanes past the last query row repeat that row (position too), so they see no such key.
+struct PrefillAttnCachedParams {
+    const unsigned short* q;       // [B, Sq, H, 128] through strides (elements): batch, sequence; head h at + 128 h
+    const unsigned short* k;       // caches [B, KVH, Lc, 128] through strides: batch, head, key
+    const unsigned short* v;
+    unsigned short* o;             // [B, Sq, H, 128]
+    long long sqb, sqs, skb, skh, sks, svb, svh, svs, sob, sos;
+    const int* kv_start;           // [B] first valid key of each sequence (left padding) or null
+    int B, Sq, H, KVH, nqb;        // Sq >= 1, any value; nqb = ceil(Sq / 128)
+    int q0, Lc;                    // position of the first query; q0 + Sq <= Lc
+    float c;                       // softmax scale * log2(e)
+};
+
+template <bool CACHED>
+struct PrefillAttnParamsOf { typedef PrefillAttnParams type; };
+template <>
+struct PrefillAttnParamsOf<true> { typedef PrefillAttnCachedParams type; };
+
+// CACHED = false is the whole-prompt kernel, instruction for instruction what it was before the parameter existed
+template <int DT, bool CACHED = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(const typename PrefillAttnParamsOf<CACHED>::type p) {
     constexpr int HD = 128, QW = 32, QB = 128, KVB = 64;
     constexpr int KROW = 272, VROW = 320;
     constexpr int K_BYTES = KVB * KROW, V_BYTES = KVB * VROW, BUF = K_BYTES + V_BYTES;
@@ -55,21 +82,42 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int h = hb % p.H, b = hb / p.H;
     const int kvh = h / (p.H / p.KVH);
     const int Q0 = qb * QB, qw0 = Q0 + wave * QW;
-    const int ks = p.kv_start ? min(max(p.kv_start[b], 0), p.S) : 0;      // device data the host cannot validate: clamp into [0, S]
+    // nrows query rows at positions q0 ..; keys 0 .. kend - 1 exist
+    const int nrows = [&] { if constexpr (CACHED) return p.Sq; else return p.S; }();
+    const int q0 = [&] { if constexpr (CACHED) return p.q0; else return 0; }();
+    const int kend = q0 + nrows;
+    const int causal = [&] { if constexpr (CACHED) return 1; else return p.causal; }();
+    const int ks = p.kv_start ? min(max(p.kv_start[b], 0), kend) : 0;     // device data the host cannot validate: clamp into [0, kend]
     const unsigned short* qp = p.q + (long long)b * p.sqb + (long long)h * HD;
-    const unsigned short* kp = p.k + (long long)b * p.skb + (long long)kvh * HD;
-    const unsigned short* vp = p.v + (long long)b * p.svb + (long long)kvh * HD;
+    const unsigned short *kp, *vp;
+    if constexpr (CACHED) {
+        kp = p.k + (long long)b * p.skb + (long long)kvh * p.skh;
+        vp = p.v + (long long)b * p.svb + (long long)kvh * p.svh;
+    } else {
+        kp = p.k + (long long)b * p.skb + (long long)kvh * HD;
+        vp = p.v + (long long)b * p.svb + (long long)kvh * HD;
+    }
     const float NEG_INF = -__builtin_inff();
 
     // this lane's query row as 8 B-operand fragments (d = 16 s + 8 hi .. + 7)
     u32x4_t qf[8];
     {
-        const int qrow = min(qw0 + l31, p.S - 1);
+        const int qrow = min(qw0 + l31, nrows - 1);
 #pragma unroll
         for (int s = 0; s < 8; ++s) qf[s] = *(const u32x4_t*)(qp + (long long)qrow * p.sqs + 16 * s + 8 * hi);
     }
-    const int last_q = min(Q0 + QB, p.S) - 1;
-    const int j_lo = ks / KVB, j_hi = (p.causal ? last_q : p.S - 1) / KVB;        // inclusive tile range of the workgroup
+    // position of this wave's first query; CACHED: lanes (and whole waves) past the last query row repeat that row, so that no lane's causal
+    // range reaches a key at or past kend
+    const int qa0 = [&] { if constexpr (CACHED) return q0 + min(qw0, nrows - 1); else return qw0; }();
+    // inclusive tile range of the workgroup.  (Two plain branches, and the whole-prompt one as it always stood: folded into one expression, or
+    // into a lambda, the compiler orders the CACHED = false kernel's prologue differently, and that kernel is to stay instruction for instruction)
+    int j_lo, j_hi;
+    if constexpr (CACHED) {
+        j_lo = ks / KVB, j_hi = (p.q0 + min(Q0 + QB, p.Sq) - 1) / KVB;
+    } else {
+        const int last_q = min(Q0 + QB, p.S) - 1;
+        j_lo = ks / KVB, j_hi = (p.causal ? last_q : p.S - 1) / KVB;
+    }
 
     // register staging: thread -> 16-byte chunk (tid & 15) of keys (tid >> 4) + 16 i
     u32x4_t kst[4], vst[4];
@@ -77,16 +125,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     auto gload = [&](int j) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const long long key = (long long)j * KVB + ld_key + 16 * i;
+            long long key = (long long)j * KVB + ld_key + 16 * i;
+            if constexpr (CACHED) key = min(key, (long long)p.Lc - 1);      // the last tile may reach past the allocation
             kst[i] = *(const u32x4_t*)(kp + key * p.sks + ld_ch * 8);
             vst[i] = *(const u32x4_t*)(vp + key * p.svs + ld_ch * 8);
         }
     };
-    auto lwrite = [&](int buf) {
+    auto lwrite = [&](int buf, int j) {
         char* base = lds + buf * BUF;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int key = ld_key + 16 * i;
+            if constexpr (CACHED) {
+                // a V row nobody wrote: zero here, after the loads had the whole compute phase to land (not in gload: it would wait for them)
+                if (j * KVB + key >= kend) vst[i] = u32x4_t{0u, 0u, 0u, 0u};
+            }
             *(u32x4_t*)(base + key * KROW + ld_ch * 16) = kst[i];
             *(u32x4_t*)(base + K_BYTES + key * VROW + ld_ch * 16) = vst[i];
         }
@@ -123,7 +176,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
     auto compute = [&](int buf, int j) {
         const int kv0 = j * KVB;
-        if (p.causal && kv0 > qw0 + QW - 1) return;                        // past this wave's diagonal (wave-uniform)
+        if (causal && kv0 > qa0 + QW - 1) return;                       // past this wave's diagonal (wave-uniform)
         const char* kb = lds + (uint32_t)(buf * BUF) + k_lane;             // + immediates: no per-read address arithmetic
         const char* vb = lds + (uint32_t)(buf * BUF + K_BYTES) + v_lane;
         f32x16_t sacc[2];
@@ -140,15 +193,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                 sacc[t] = mfma32<DT>(kf, qf[s], sacc[t]);
             }
         // masks: keys past the query (causal) or before the first valid key (left padding); only on tiles that straddle either edge
-        const bool edge = (p.causal && kv0 + KVB - 1 > qw0) || ks > kv0;
+        const bool edge = (causal && kv0 + KVB - 1 > qa0) || ks > kv0;
         if (edge) {
-            const int q_abs = qw0 + l31;
+            const int q_abs = [&] { if constexpr (CACHED) return q0 + min(qw0 + l31, nrows - 1); else return qw0 + l31; }();
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key_abs = kv0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if ((p.causal && key_abs > q_abs) || key_abs < ks) sacc[t][r] = NEG_INF;
+                    if ((causal && key_abs > q_abs) || key_abs < ks) sacc[t][r] = NEG_INF;
                 }
         }
         float mx = sacc[0][0];
@@ -198,7 +251,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
     if (j_lo <= j_hi) {
         gload(j_lo);
-        lwrite(0);
+        lwrite(0, j_lo);
         // every load so far (the query fragments too) has landed BEFORE the loop: left pending, the compiler's wait-count pass carries them
         // across the back edge and makes each QK^T MFMA of every tile wait for the loads of the NEXT tile issued just above it
         __builtin_amdgcn_s_waitcnt(0x0f70);                                // vmcnt(0)
@@ -207,7 +260,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             const int cur = (j - j_lo) & 1;
             if (j < j_hi) gload(j + 1);
             compute(cur, j);
-            if (j < j_hi) lwrite(cur ^ 1);
+            if (j < j_hi) lwrite(cur ^ 1, j + 1);
             __syncthreads();
         }
     }
@@ -231,7 +284,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int i = 0; i < 8; ++i) {
         const int row = 4 * i + (lane >> 4), ch = lane & 15;
         const u32x4_t val = *(const u32x4_t*)(ob + row * OROW + ch * 16);
-        if (qw0 + row < p.S) *(u32x4_t*)(op + (long long)(qw0 + row) * p.sos + ch * 8) = val;
+        if (qw0 + row < nrows) *(u32x4_t*)(op + (long long)(qw0 + row) * p.sos + ch * 8) = val;
     }
 }
 

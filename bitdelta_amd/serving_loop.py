@@ -688,6 +688,20 @@ class TenantDecoder(nn.Module):
             if not (S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd)):
                 raise RuntimeError("a ragged decode step needs the HIP decode attention (fast_glue, head_dim 128, 1 / 4 / 8 query heads per kv head)")
             a = ops.decode_attention_ragged(qkv, self.cos, self.sin, ck, cv, cache["valid"], ragged[0], ragged[1], heads, kvh)
+        elif (cache.get("chunk") is not None and self.fast_glue and self.hip_prefill_attention and hd == 128 and qkv.is_contiguous()
+              and not layer.qkv.interleave8):
+            # a chunk of S rows at positions q0 .. q0 + S - 1 behind cached keys (prefill_chunk): RoPE of q and k at those positions + both cache
+            # writes, then flash-style attention of the chunk's queries over the cache rows kv_start[t] .. their own position.  With the switch
+            # off the chunk takes the branches below (S > 1: rope + SDPA over the [T, 1, S, Lc] mask; S == 1: the decode launch at pos_idx)
+            q0, kvs = cache["chunk"]
+            nq, nk = heads * hd, kvh * hd
+            if ck.is_contiguous() and cv.is_contiguous():
+                ops.rope_kv_append_(qkv, self.cos, self.sin, ck, cv, heads, kvh, q0)
+            else:
+                ops.rope_(qkv[..., :nq + nk], self.cos, self.sin, heads + kvh, S, q0)
+                ck[:, :, q0:q0 + S] = qkv[..., nq:nq + nk].view(T, S, kvh, hd).transpose(1, 2)
+                cv[:, :, q0:q0 + S] = qkv[..., nq + nk:].view(T, S, kvh, hd).transpose(1, 2)
+            a = ops.prefill_attention_cached(qkv[..., :nq].view(T, S, heads, hd), ck, cv, q0, kv_start=kvs)
         elif S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd):
             # decode: RoPE + cache append + attention over the valid keys in ONE launch (pos_idx is a one-element device tensor)
             a = ops.decode_attention(qkv, self.cos, self.sin, ck, cv, cache["valid"], pos_idx, heads, kvh)
@@ -767,7 +781,8 @@ class TenantDecoder(nn.Module):
         assert ragged is None or S == 1
         # (the rows of the rotary tables are gathered only for the stock-op attention paths: the HIP kernels index the tables themselves)
         hip_attn = self.fast_glue and ((S == 1 and ops.decode_attention_supported(heads, kvh, self.hd)) or
-                                       (S > 1 and cache.get("kv_start") is not None and self.hd == 128 and S % 64 == 0))
+                                       (S > 1 and cache.get("kv_start") is not None and self.hd == 128 and S % 64 == 0) or
+                                       (cache.get("chunk") is not None and self.hip_prefill_attention and self.hd == 128))
         cos, sin = (None, None) if (hip_attn or ragged is not None) else (self.cos[pos_idx], self.sin[pos_idx])
         if x is None:
             t_idx = torch.arange(T, device=ids.device).view(T, 1)
@@ -815,6 +830,28 @@ class TenantDecoder(nn.Module):
             return self.forward(ids, pos_idx, cache, mask)
         finally:
             cache["kv_start"] = None
+
+    @torch.no_grad()
+    def prefill_chunk(self, ids, q0, cache, kv_start=None):
+        """Prefill ids [T, n] (n >= 1, any value) at positions q0 .. q0 + n - 1 BEHIND the keys already in the cache -- the next turn of a
+        conversation whose rows 0 .. q0 - 1 are cached, where the reference re-prefills the whole history (demo/demo_backend.py:261-315).
+        Marks valid[:, q0 : q0 + n], writes those cache rows and returns the last row's logits [T, vocab].  kv_start: int32 [T] device tensor,
+        each tenant's first valid key (its left pads; None = 0).  hip_prefill_attention picks the arm: bd_srv_prefill_attention_cached, or the
+        stock ops (rope + SDPA over a [T, 1, n, Lc] mask made of the validity bytes)."""
+        T, n = ids.shape
+        q0 = int(q0)
+        Lc = cache["k"][0].shape[2]
+        if not (n >= 1 and 0 <= q0 and q0 + n <= Lc):
+            raise ValueError("the chunk's rows %d .. %d do not lie in the KV cache (%d rows)" % (q0, q0 + n - 1, Lc))
+        pos_idx = torch.arange(q0, q0 + n, device=self.dev)
+        cache["valid"][:, q0:q0 + n] = True
+        seen = torch.arange(Lc, device=self.dev)[None, :] <= pos_idx[:, None]                    # query i sees keys <= q0 + i
+        mask = seen[None, None] & cache["valid"][:, None, None, :]
+        cache["chunk"] = (q0, kv_start)
+        try:
+            return self.forward(ids, pos_idx, cache, mask)
+        finally:
+            cache["chunk"] = None
 
     def _decode_step(self, st):
         """one greedy step on static buffers: st['tok'] [T,1] -> logits -> argmax -> st['tok']; position / masks advance on device"""
@@ -960,6 +997,29 @@ class TenantDecoder(nn.Module):
         return g.replay
 
 
+def extend_plan(pos, kv_start, done, n_tokens, Lc, active=False):
+    """Geometry and refusals of TenantSession.extend, host integers only: a retired tenant at position `pos` (its cache rows hold the conversation
+    up to, not including, its last emitted token) whose conversation starts at row kv_start (the left pads of its first prompt; None = never
+    submitted, or its fine-tune was replaced since) takes n_tokens more tokens.  Returns (P, n): the chunk [last emitted token] + tokens has
+    n = 1 + n_tokens rows and goes to cache rows P .. P + n - 1.  Raises, in this order: RuntimeError for an active tenant, for one without a
+    cached conversation, and for one whose cache rows are full (done & 4); ValueError when the chunk does not fit the Lc cache rows, and when the
+    conversation's real length, padded as a request of that length would be, passes MAX_PROMPT (the reference's refusal)."""
+    if active:
+        raise RuntimeError("the tenant is still generating")
+    if kv_start is None:
+        raise RuntimeError("the tenant has no cached conversation to extend (never submitted, or its fine-tune was replaced)")
+    if int(done) & 4:
+        raise RuntimeError("the tenant's cache rows are full")
+    P, n = int(pos), 1 + int(n_tokens)
+    if not (0 <= int(kv_start) <= P and n_tokens >= 0):
+        raise ValueError("position %d / first key %d / %d new tokens: not a conversation's state" % (P, kv_start, n_tokens))
+    if P + n > Lc:
+        raise ValueError("the conversation does not fit the KV cache")
+    if padded_length(P - int(kv_start) + n) > MAX_PROMPT:
+        raise ValueError("max_len too large, please reduce the input length")
+    return P, n
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -996,6 +1056,7 @@ class TenantSession:
         self.stop_ids = torch.full((T, max(int(max_stop_ids), 1)), -1, dtype=torch.long, device=dev)
         self.out = torch.zeros(T, dec.max_len, dtype=torch.long, device=dev)      # (a caller may swap in a strided view BEFORE the first step)
         self._graphs = {}
+        self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
         dec._sessions.add(self)
 
     # ------------------------------------------------------------ admission
@@ -1010,6 +1071,7 @@ class TenantSession:
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
         rescaled = self.dec.load_tenant(t, state)
+        self._kv_start[t] = None                      # the cache rows belong to the fine-tune that left: nothing to extend
         self.cache["valid"][t].zero_()
         self.done[t] = 0
         self.n[t] = 0
@@ -1058,6 +1120,33 @@ class TenantSession:
         am[0, L - len(prompt):] = True
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
         self._admit(t, int(torch.argmax(logits, dim=-1)[0]), L, max_new_tokens, stops)
+        self._kv_start[t] = L - len(prompt)
+
+    @torch.no_grad()
+    def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=()):
+        """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
+        submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
+        request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
+        token, so the chunk is [that token] + tokens at rows P .. P + n - 1, P = pos[t]; it runs through tenant_view(t).prefill_chunk, and the
+        tenant is admitted as after a submit of P + n rows: result(t) restarts with this turn's tokens.  Refusals (extend_plan), all raised
+        before any state or cache row is touched: an active tenant, one never submitted or whose fine-tune was replaced since (RuntimeError), one
+        whose cache rows are full (RuntimeError), a chunk that does not fit the cache, a conversation whose padded real length passes MAX_PROMPT
+        (ValueError).  Nobody else's state, cache rows or validity bytes are touched, and the captured step is reused.  One host read before the
+        prefill (tenant t's activity flag, position, stop reason and last token together) and, as in submit, one of the first token after it.
+        The conversation is the decoder's cache rows: a generate() on the decoder ends it
+        without the session knowing."""
+        dec = self.dec
+        if not (isinstance(t, int) and 0 <= t < self.T):
+            raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
+        assert max_new_tokens >= 1
+        tokens = [int(i) for i in tokens]
+        stops = self._stops(stop_token_ids)
+        active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
+        P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
+        ids = torch.tensor([[last] + tokens], dtype=torch.long).to(dec.dev)
+        kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
+        logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
+        self._admit(t, int(torch.argmax(logits, dim=-1)[0]), P + n, max_new_tokens, stops)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None):
@@ -1075,6 +1164,7 @@ class TenantSession:
         first = torch.argmax(dec.prefill(ids, am, self.cache), dim=-1).tolist()
         for t in range(self.T):
             self._admit(t, first[t], L, max_new_tokens, stops[t])
+            self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
     def _step_once(self):

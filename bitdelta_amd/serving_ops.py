@@ -142,6 +142,42 @@ def prefill_attention(q, k, v, kv_start=None, causal=True, scale=None):
     return out
 
 
+def prefill_attention_cached_supported(q, kcache, vcache, q0=0):
+    """the shapes bd_srv_prefill_attention_cached takes: q a [B, Sq, heads, 128] view (batch / sequence strides multiples of 8 elements, heads
+    contiguous, Sq >= 1), the caches [B, kv_heads, Lc, 128] (any batch / head / key strides that are multiples of 8), 0 <= q0 and q0 + Sq <= Lc"""
+    if q.dim() != 4 or kcache.dim() != 4 or q.shape[3] != 128 or q.dtype not in DTYPE_CODE or q.shape[1] < 1 or q.shape[2] % kcache.shape[1]:
+        return False
+    if q.stride(3) != 1 or q.stride(2) != 128 or q.stride(1) % 8 or q.stride(0) % 8 or q.data_ptr() % 16:
+        return False
+    for t in (kcache, vcache):
+        if t.stride(3) != 1 or t.stride(2) % 8 or t.stride(1) % 8 or t.stride(0) % 8 or t.data_ptr() % 16:
+            return False
+    return (kcache.shape == vcache.shape and kcache.shape[0] == q.shape[0] and kcache.shape[3] == 128 and kcache.dtype == q.dtype == vcache.dtype
+            and 0 <= q0 and q0 + q.shape[1] <= kcache.shape[2])
+
+
+def prefill_attention_cached(q, kcache, vcache, q0, kv_start=None, scale=None):
+    """Causal flash-style attention of a chunk of queries at positions q0 .. q0 + Sq - 1 over the keys in the KV caches (the chunk's own rows
+    already appended: rope_kv_append_(..., pos0=q0)).  q [B, Sq, heads, 128] -- the q slice of a fused q|k|v projection output is fine;
+    kcache / vcache [B, kv_heads, Lc, 128]; kv_start: optional int32 [B] device tensor, first valid key of each sequence (left padding).
+    Cache rows at or past q0 + Sq are not trusted.  Returns [B, Sq, heads * 128] (what the o projection consumes)."""
+    require_gpu(q, kcache, vcache)
+    q0 = int(q0)
+    assert prefill_attention_cached_supported(q, kcache, vcache, q0), "prefill_attention_cached: unsupported geometry"
+    B, Sq, H, hd = q.shape
+    out = torch.empty((B, Sq, H * hd), device=q.device, dtype=q.dtype)
+    if kv_start is not None:
+        assert kv_start.dtype == torch.int32 and kv_start.is_cuda and kv_start.numel() == B and kv_start.is_contiguous()
+    with torch.cuda.device(q.device):
+        check(lib().bd_srv_prefill_attention_cached(ptr(q), ptr(kcache), ptr(vcache), ptr(out), B, Sq, H, kcache.shape[1], hd, q0, kcache.shape[2],
+                                                    q.stride(0), q.stride(1), kcache.stride(0), kcache.stride(1), kcache.stride(2),
+                                                    vcache.stride(0), vcache.stride(1), vcache.stride(2), out.stride(0), out.stride(1),
+                                                    ptr(kv_start) if kv_start is not None else None,
+                                                    float(scale if scale is not None else hd ** -0.5), DTYPE_CODE[q.dtype], stream_ptr()),
+              "srv_prefill_attention_cached")
+    return out
+
+
 def cache_warm(a, b=None, blocks=0):
     """Read tensor a (and b) and discard the values on the CURRENT stream: the weight-prefetch node of a hipGraph side branch
     (serving_loop.TenantDecoder.prefetch_o).  Contiguous device tensors; whole 16-byte chunks are touched."""

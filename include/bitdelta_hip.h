@@ -317,6 +317,21 @@ int bd_srv_decode_attention_ragged(const void* QKV, const void* cos_t, const voi
 int bd_srv_prefill_attention(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
                              int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs, int64_t sob, int64_t sos,
                              const int32_t* kv_start, float scale, int causal, int dtype, void* stream);
+/* bd_srv_prefill_attention_cached: bd_srv_prefill_attention for a CHUNK of Sq queries at positions q0 .. q0 + Sq - 1 over the keys already in the
+ *   KV caches -- the next turn of a conversation whose earlier turns are cached (the reference re-sends and re-prefills the whole history with
+ *   every request, demo/demo_backend.py:261-315), or one chunk of a long prompt.  Always causal:
+ *   O[b, i, h] = softmax_k(Q[b, i, h] . Kc[b, h / (H/KVH), k] * scale) . Vc[b, h / (H/KVH), k] over kv_start[b] <= k <= q0 + i, i = 0 .. Sq - 1.
+ *   Q / O as there ([B, Sq, H, 128] through batch and sequence strides: the q slice of the fused projection output as it lies); Kc / Vc are the
+ *   caches [B, KVH, Lc, 128] through batch, head and key strides (skb, skh, sks / svb, svh, svs, elements), read AFTER bd_srv_rope_kv_append
+ *   (pos0 = q0) has written the chunk's own rows.  Same tile walk and per-row arithmetic as bd_srv_prefill_attention: row i is bit for bit row
+ *   q0 + i of that call over the whole sequence.  Cache rows at or past q0 + Sq are never trusted: addresses are clamped into [0, Lc), such a
+ *   key's score is masked and its V row is zeroed before the matrix product, so a non-finite bit pattern there reaches no output.  kv_start [B]
+ *   int32 on the device or NULL, clamped into [0, q0 + Sq] in the kernel; query rows with no valid key return 0.
+ *   BD_E_BAD_SHAPE, from host checks that run before any device call: head_dim != 128, H % KVH != 0, Sq < 1, q0 < 0, q0 + Sq > Lc, a stride that
+ *   is not a multiple of 8, a pointer that is not 16-byte aligned.  B == 0 is an empty call (BD_OK). */
+int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim, int q0,
+                                    int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb, int64_t svh,
+                                    int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int dtype, void* stream);
 /* scratch for bd_srv_decode_attention's split of the key range over 4 blocks per (tenant, kv head) (up to 16 for one or two sequences of a
  * grouped-query model; the size returned covers the largest split count and depends on the geometry only), merged inside the launch by the
  * block that finishes last (0 = the cache is short enough to run unsplit; ws may then be NULL).  Without a workspace the kernel
