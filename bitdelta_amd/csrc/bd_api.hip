@@ -1879,6 +1879,53 @@ extern "C" int bd_srv_step_end_ragged(const void* logits, int64_t sl, int V, int
     return launch_status();
 }
 
+static inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+extern "C" int bd_srv_sample_rows(const void* logits, int64_t sl, int V, const float* temperature, const int32_t* top_k, const float* top_p,
+                                  const int64_t* seed, const int64_t* draw, int64_t* tok, int32_t* dbg, int R, int dtype, void* stream) {
+    if (R < 0 || V < 1) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (!logits || !temperature || !top_k || !top_p || !seed || !draw || !tok) return BD_E_NULL;
+    if (V % 8 || sl % 8 || sl < V || !aligned16(logits) || !aligned_to(temperature, 4) || !aligned_to(top_k, 4) || !aligned_to(top_p, 4) ||
+        !aligned_to(seed, 8) || !aligned_to(draw, 8) || !aligned_to(tok, 8) || !aligned_to(dbg, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == BD_BF16)
+        hipLaunchKernelGGL((sample_rows_kernel<DT_BF16>), dim3((unsigned)R), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           temperature, (const int*)top_k, top_p, (const long long*)seed, (const long long*)draw, (long long*)tok, (int*)dbg);
+    else
+        hipLaunchKernelGGL((sample_rows_kernel<DT_F16>), dim3((unsigned)R), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           temperature, (const int*)top_k, top_p, (const long long*)seed, (const long long*)draw, (long long*)tok, (int*)dbg);
+    return launch_status();
+}
+
+extern "C" int bd_srv_step_end_sample(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
+                                      const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done,
+                                      int Lc, const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seed,
+                                      int32_t* dbg, int T, int dtype, void* stream) {
+    if (T < 0 || V < 1 || ns < 0 || out_cap < 0 || Lc < 1) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (T == 0) return BD_OK;
+    if (!logits || !tok || !out || !pos || !n || !limit || !active || !done || (ns > 0 && !stop_ids) || !temperature || !top_k || !top_p || !seed)
+        return BD_E_NULL;
+    if (V % 8 || sl % 8 || sl < V || s_out < out_cap || !aligned16(logits) || !aligned_to(temperature, 4) || !aligned_to(top_k, 4) ||
+        !aligned_to(top_p, 4) || !aligned_to(seed, 8) || !aligned_to(dbg, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == BD_BF16)
+        hipLaunchKernelGGL((step_end_sample_kernel<DT_BF16>), dim3((unsigned)T), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           (long long*)tok, (long long*)out, (long long)s_out, out_cap, (const long long*)stop_ids, ns, (long long*)pos,
+                           (long long*)n, (const long long*)limit, (unsigned char*)active, (unsigned char*)done, Lc, temperature,
+                           (const int*)top_k, top_p, (const long long*)seed, (int*)dbg);
+    else
+        hipLaunchKernelGGL((step_end_sample_kernel<DT_F16>), dim3((unsigned)T), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,
+                           (long long*)tok, (long long*)out, (long long)s_out, out_cap, (const long long*)stop_ids, ns, (long long*)pos,
+                           (long long*)n, (const long long*)limit, (unsigned char*)active, (unsigned char*)done, Lc, temperature,
+                           (const int*)top_k, top_p, (const long long*)seed, (int*)dbg);
+    return launch_status();
+}
+
 extern "C" int bd_srv_cache_warm(const void* p0, int64_t bytes0, const void* p1, int64_t bytes1, int blocks, void* stream) {
     if (bytes0 < 0 || bytes1 < 0 || blocks < 0) return BD_E_BAD_SHAPE;
     if ((bytes0 && !p0) || (bytes1 && !p1)) return BD_E_NULL;

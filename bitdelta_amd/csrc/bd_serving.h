@@ -408,6 +408,320 @@ __global__ void __launch_bounds__(256) step_end_ragged_kernel(const unsigned sho
     }
 }
 
+// ---- Sampling (temperature, top-k, top-p, seed): one logits row -> one token, a pure function of the row and (tau, top_k, top_p, seed, d).
+// include/bitdelta_hip.h (bd_srv_sample_rows) is the definition; tests/sampling_ref.py restates it in fp64.  One 256-thread block per row, the row
+// is read from global memory (64 KB at V = 32000: L2-resident after the lm_head) once per pass, never staged in LDS.  Passes, each skipped when
+// the row does not need it: argmax + NaN / +inf flag; top-k threshold (exact radix select on the monotone 16-bit key, high byte then low byte);
+// top-p threshold (fixed-point masses per key byte, high byte then low byte inside the boundary bin); Gumbel argmax over the kept keys.  Every
+// sum that decides a threshold is an integer sum in LDS (order-independent); no floating-point atomics.
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key (k0, k1) -> c[4]
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
+        c[0] = h1 ^ c[1] ^ k0; c[1] = l1; c[2] = h0 ^ c[3] ^ k1; c[3] = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+// -log(-log u), u = ((r >> 8) + 0.5) * 2^-24 in (0, 1).  The argument of the inner logarithm is formed exactly: u itself below 1/2 (an odd
+// integer below 2^24, scaled), u - 1 from 1/2 on (likewise), so -log u keeps its relative accuracy down to u -> 1 where it is ~2^-25.
+// The hardware logarithm (v_log_f32, 1 ulp) keeps that relative accuracy wherever its result is not near 0: below 1/2 it takes u, and the outer
+// logarithm needs absolute accuracy only.  From 1/2 on, -log u = -log(1 - t) = 2 atanh(t / (2 - t)) with t = 1 - u exact and t / (2 - t) <= 1/3:
+// the odd series to s^13 (next term < 2e-8 of the sum).
+__device__ __forceinline__ float gumbel_from_word(uint32_t r) {
+    const int n2 = (int)(2u * (r >> 8) + 1u);                            // u * 2^25: odd, 1 .. 2^25 - 1
+    float a;
+    if (n2 < (1 << 24)) {
+        a = -0.69314718056f * __log2f((float)n2 * 0x1p-25f);
+    } else {
+        const float t = (float)((1 << 25) - n2) * 0x1p-25f, sq = t / (2.f - t), z = sq * sq;
+        float pl = 1.f / 13.f;
+        pl = fmaf(pl, z, 1.f / 11.f); pl = fmaf(pl, z, 1.f / 9.f); pl = fmaf(pl, z, 1.f / 7.f);
+        pl = fmaf(pl, z, 1.f / 5.f); pl = fmaf(pl, z, 1.f / 3.f); pl = fmaf(pl, z, 1.f);
+        a = 2.f * sq * pl;
+    }
+    return -0.69314718056f * __log2f(a);
+}
+// monotone 16-bit key of a 16-bit float's bits (sign-magnitude -> unsigned order); -0 and +0 are one VALUE and get one key
+__device__ __forceinline__ uint32_t sample_key(uint32_t b) {
+    if ((b & 0x7fffu) == 0u) b = 0u;
+    return b ^ ((b & 0x8000u) ? 0xffffu : 0x8000u);
+}
+__device__ __forceinline__ uint32_t sample_key_bits(uint32_t k) { return k ^ ((k & 0x8000u) ? 0x8000u : 0xffffu); }
+// exp((l - m) / tau) in 2^-40 fixed point: m is the row's finite maximum, so the result is 0 .. 2^40 and a row of 2^17 tokens sums below 2^58
+// (hardware exp2: ~1e-7 relative, times the |exponent| for the scaling by log2 e -- a few 1e-6 at the small masses, far inside the 1e-4 at
+// which a row counts as decisive)
+__device__ __forceinline__ unsigned long long sample_mass(float l, float m, float tau) {
+    return (unsigned long long)(__expf((l - m) / tau) * 0x1p40f);
+}
+enum : int { SAMPLE_GREEDY = 1, SAMPLE_TOPK = 2, SAMPLE_TOPP = 4, SAMPLE_SPECIAL = 8 };
+
+struct SampleLds {
+    unsigned long long hist[256];
+    unsigned long long sel[4];              // 0: the selected bin, 1: the sum above it (base included), 2: the histogram's total, 3: the top-p target
+    float bv[4];
+    int bi[4];
+    int flag[4];
+    uint32_t cnt[4], kmin[4];
+};
+
+// One pass over a row: f(c, v) for every 16-byte vector v = row[c .. c + 7].  Four loads are in flight per trip (a trip is a dependent L2 round
+// trip, and one block per row has nothing else to hide it behind); a load past the row is redirected to the trip's first vector and dropped.
+template <class F>
+__device__ __forceinline__ void sample_sweep(const unsigned short* __restrict__ row, int V, F&& f) {
+    for (int c = threadIdx.x * 8; c < V; c += 4 * 256 * 8) {
+        u32x4_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *(const u32x4_t*)(row + (c + 2048 * j < V ? c + 2048 * j : c));
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (c + 2048 * j < V) f(c + 2048 * j, v[j]);
+    }
+}
+
+// Wave 0: the LOWEST bin b of hist[256] with base + sum(hist[b + 1 ..]) < target -- the bin that holds the k-th largest key (target = k) or the
+// nucleus' boundary value (target = ceil(top_p * Z)).  frac > 0: target = ceil(frac * total) (and is left in sel[3]).  Bin 255 always
+// qualifies when target > base.  Integer sums in a fixed order: exact.
+__device__ __forceinline__ void sample_select(SampleLds& s, unsigned long long base, unsigned long long target, float frac) {
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        unsigned long long h[4], x = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { h[j] = s.hist[4 * lane + j]; x += h[j]; }
+        const unsigned long long own = x;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {                         // inclusive suffix sum over the lanes
+            const unsigned long long o = __shfl_down(x, off, 64);
+            if (lane + off < 64) x += o;
+        }
+        const unsigned long long total = __shfl(x, 0, 64);
+        if (frac > 0.f) {
+            const double tf = ceil((double)frac * (double)total);
+            target = tf < 1.0 ? 1ull : (unsigned long long)tf;
+        }
+        unsigned long long above = base + (x - own), a_sel = 0;
+        int b_sel = 256;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            if (above < target) { b_sel = 4 * lane + j; a_sel = above; }
+            above += h[j];
+        }
+        int b_min = b_sel;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(b_min, off, 64); b_min = o < b_min ? o : b_min; }
+        if (b_min == 256 && lane == 63) { b_sel = 255; b_min = 255; a_sel = base; }      // (target <= base: cannot happen; keep the top bin)
+        if (b_sel == b_min && b_sel < 256) { s.sel[0] = (unsigned long long)b_sel; s.sel[1] = a_sel; }
+        if (lane == 0) { s.sel[2] = total; s.sel[3] = target; }
+    }
+    __syncthreads();
+}
+
+// The token of one row, valid in thread 0 (all 256 threads of the block must call it: it has barriers).  dbg (or NULL): int32[4] = kept count,
+// 16-bit pattern of the smallest kept logit value, the chosen token's Philox word, flags (SAMPLE_*); the greedy rule leaves the first three at 0.
+// Device values the host cannot see are neutralised: tau not in (0, inf) -> greedy; top_k < 1 or >= V -> off; top_p not in (0, 1) -> off.
+template <int DT>
+__device__ __forceinline__ int sample_row(const unsigned short* __restrict__ row, int V, float tau, int top_k, float top_p,
+                                          unsigned long long seed, unsigned long long d, int* __restrict__ dbg) {
+    __shared__ SampleLds s;
+    constexpr uint32_t KEY_NINF = DT == DT_BF16 ? 0x007fu : 0x03ffu;   // sample_key(-inf); finite values lie above it (no NaN / +inf past pass 0)
+    const int tid = threadIdx.x;
+    // ---- pass 0: argmax in torch's order, and whether the row holds a NaN or +inf
+    float best = -__builtin_inff();
+    int bidx = 0x7fffffff, special = 0;
+    sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float lo = half_bits_to_f32<DT>(v[e] & 0xffffu), hi = half_bits_to_f32<DT>(v[e] >> 16);
+            special |= (!(lo < __builtin_inff())) | (!(hi < __builtin_inff()));
+            if (argmax_better(lo, c + 2 * e, best, bidx)) { best = lo; bidx = c + 2 * e; }
+            if (argmax_better(hi, c + 2 * e + 1, best, bidx)) { best = hi; bidx = c + 2 * e + 1; }
+        }
+    });
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bidx, off, 64);
+        special |= __shfl_xor(special, off, 64);
+        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
+    }
+    if ((tid & 63) == 0) { s.bv[tid >> 6] = best; s.bi[tid >> 6] = bidx; s.flag[tid >> 6] = special; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {                                       // every thread folds the four waves: the result is block-uniform
+        special |= s.flag[w];
+        if (argmax_better(s.bv[w], s.bi[w], best, bidx)) { best = s.bv[w]; bidx = s.bi[w]; }
+    }
+    special |= !(best > -__builtin_inff());                             // nothing finite: the greedy rule decides
+    const bool k_on = top_k >= 1 && top_k < V, p_on = top_p > 0.f && top_p < 1.f;
+    const int filt = (k_on ? SAMPLE_TOPK : 0) | (p_on ? SAMPLE_TOPP : 0);
+    if (!(tau > 0.f && tau < __builtin_inff()) || special) {
+        if (dbg && tid == 0) { dbg[0] = 0; dbg[1] = 0; dbg[2] = 0; dbg[3] = SAMPLE_GREEDY | (special ? SAMPLE_SPECIAL : 0) | filt; }
+        return bidx;
+    }
+    const float m = best;
+    uint32_t kthr = 0;                                                  // keys >= kthr are kept
+    // ---- top-k: the key of the k-th largest logit, high byte then low byte
+    if (k_on) {
+        s.hist[tid] = 0;
+        __syncthreads();
+        sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                atomicAdd(&s.hist[sample_key(v[e] & 0xffffu) >> 8], 1ull);
+                atomicAdd(&s.hist[sample_key(v[e] >> 16) >> 8], 1ull);
+            }
+        });
+        __syncthreads();
+        sample_select(s, 0ull, (unsigned long long)top_k, 0.f);
+        const uint32_t hb = (uint32_t)s.sel[0];
+        const unsigned long long above = s.sel[1];
+        s.hist[tid] = 0;
+        __syncthreads();
+        sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t k0 = sample_key(v[e] & 0xffffu), k1 = sample_key(v[e] >> 16);
+                if ((k0 >> 8) == hb) atomicAdd(&s.hist[k0 & 0xffu], 1ull);
+                if ((k1 >> 8) == hb) atomicAdd(&s.hist[k1 & 0xffu], 1ull);
+            }
+        });
+        __syncthreads();
+        sample_select(s, above, (unsigned long long)top_k, 0.f);
+        kthr = (hb << 8) | (uint32_t)s.sel[0];
+    }
+    if (kthr <= KEY_NINF) kthr = KEY_NINF + 1;                          // -inf has weight 0 and is never sampled
+    // ---- top-p over the top-k survivors: the smallest value whose mass of strictly larger values is below top_p * Z
+    if (p_on) {
+        s.hist[tid] = 0;
+        __syncthreads();
+        sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t k0 = sample_key(v[e] & 0xffffu), k1 = sample_key(v[e] >> 16);
+                if (k0 >= kthr) atomicAdd(&s.hist[k0 >> 8], sample_mass(half_bits_to_f32<DT>(v[e] & 0xffffu), m, tau));
+                if (k1 >= kthr) atomicAdd(&s.hist[k1 >> 8], sample_mass(half_bits_to_f32<DT>(v[e] >> 16), m, tau));
+            }
+        });
+        __syncthreads();
+        sample_select(s, 0ull, 0ull, top_p);
+        const uint32_t hb = (uint32_t)s.sel[0];
+        const unsigned long long above = s.sel[1], target = s.sel[3];
+        s.hist[tid] = 0;
+        __syncthreads();
+        sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t k0 = sample_key(v[e] & 0xffffu), k1 = sample_key(v[e] >> 16);
+                if (k0 >= kthr && (k0 >> 8) == hb) atomicAdd(&s.hist[k0 & 0xffu], sample_mass(half_bits_to_f32<DT>(v[e] & 0xffffu), m, tau));
+                if (k1 >= kthr && (k1 >> 8) == hb) atomicAdd(&s.hist[k1 & 0xffu], sample_mass(half_bits_to_f32<DT>(v[e] >> 16), m, tau));
+            }
+        });
+        __syncthreads();
+        sample_select(s, above, target, 0.f);
+        const uint32_t pthr = (hb << 8) | (uint32_t)s.sel[0];
+        if (pthr > kthr) kthr = pthr;
+    }
+    // ---- the draw: argmax of l / tau - log(-log u) over the kept keys, ties to the lower index
+    const uint32_t sk0 = (uint32_t)seed, sk1 = (uint32_t)(seed >> 32), d0 = (uint32_t)d, d1 = (uint32_t)(d >> 32);
+    best = -__builtin_inff();
+    bidx = 0x7fffffff;
+    uint32_t cnt = 0, kmin = 0xffffu;
+    sample_sweep(row, V, [&](int c, u32x4_t v) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {                                   // tokens c + 4q .. c + 4q + 3 share one Philox block
+            uint32_t bits[4], key[4];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                bits[j] = (v[2 * q + (j >> 1)] >> (16 * (j & 1))) & 0xffffu;
+                key[j] = sample_key(bits[j]);
+                any |= key[j] >= kthr;
+            }
+            if (!any) continue;
+            uint32_t w[4] = {(uint32_t)((c >> 2) + q), 0u, d0, d1};
+            philox4x32_10(w, sk0, sk1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (key[j] < kthr) continue;
+                const float sc = half_bits_to_f32<DT>(bits[j]) / tau + gumbel_from_word(w[j]);
+                const int i = c + 4 * q + j;
+                ++cnt;
+                kmin = key[j] < kmin ? key[j] : kmin;
+                if (argmax_better(sc, i, best, bidx)) { best = sc; bidx = i; }
+            }
+        }
+    });
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bidx, off, 64);
+        const uint32_t oc = __shfl_xor(cnt, off, 64), ok = __shfl_xor(kmin, off, 64);
+        cnt += oc;
+        kmin = ok < kmin ? ok : kmin;
+        if (argmax_better(ov, oi, best, bidx)) { best = ov; bidx = oi; }
+    }
+    __syncthreads();                                                    // (every wave has folded pass 0's partials out of bv / bi)
+    if ((tid & 63) == 0) { s.bv[tid >> 6] = best; s.bi[tid >> 6] = bidx; s.cnt[tid >> 6] = cnt; s.kmin[tid >> 6] = kmin; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            cnt += s.cnt[w];
+            kmin = s.kmin[w] < kmin ? s.kmin[w] : kmin;
+            if (argmax_better(s.bv[w], s.bi[w], best, bidx)) { best = s.bv[w]; bidx = s.bi[w]; }
+        }
+        bidx = bidx < 0 ? 0 : (bidx >= V ? V - 1 : bidx);               // (the maximum is always kept, so a token was chosen; the result is in [0, V) regardless)
+        if (dbg) {
+            uint32_t w[4] = {(uint32_t)(bidx >> 2), 0u, d0, d1};
+            philox4x32_10(w, sk0, sk1);
+            dbg[0] = (int)cnt; dbg[1] = (int)sample_key_bits(kmin); dbg[2] = (int)w[bidx & 3]; dbg[3] = filt;
+        }
+    }
+    return bidx;
+}
+
+// R independent rows, each with its own (tau, top_k, top_p, seed, d): tok[r] only.  Admission (the first token, from the prefill's logits).
+template <int DT>
+__global__ void __launch_bounds__(256) sample_rows_kernel(const unsigned short* __restrict__ logits, long long sl, int V,
+                                                          const float* __restrict__ tau, const int* __restrict__ top_k,
+                                                          const float* __restrict__ top_p, const long long* __restrict__ seed,
+                                                          const long long* __restrict__ draw, long long* __restrict__ tok, int* __restrict__ dbg) {
+    const int r = blockIdx.x;
+    const int nxt = sample_row<DT>(logits + (long long)r * sl, V, tau[r], top_k[r], top_p[r], (unsigned long long)seed[r],
+                                   (unsigned long long)draw[r], dbg ? dbg + 4 * (long long)r : nullptr);
+    if (threadIdx.x == 0) tok[r] = nxt;
+}
+
+// step_end_ragged_kernel's state update with the token from sample_row; d = pos[t] + 1, the cache row the new token will occupy.
+template <int DT>
+__global__ void __launch_bounds__(256) step_end_sample_kernel(const unsigned short* __restrict__ logits, long long sl, int V, long long* __restrict__ tok,
+                                                              long long* __restrict__ out, long long s_out, int out_cap,
+                                                              const long long* __restrict__ stop_ids, int ns, long long* __restrict__ pos,
+                                                              long long* __restrict__ n, const long long* __restrict__ limit,
+                                                              unsigned char* __restrict__ active, unsigned char* __restrict__ done, int Lc,
+                                                              const float* __restrict__ tau, const int* __restrict__ top_k,
+                                                              const float* __restrict__ top_p, const long long* __restrict__ seed,
+                                                              int* __restrict__ dbg) {
+    const int t = blockIdx.x;
+    if (active[t] == 0) return;                                         // uniform over the block
+    const long long p1 = pos[t] + 1;
+    const int bidx = sample_row<DT>(logits + (long long)t * sl, V, tau[t], top_k[t], top_p[t], (unsigned long long)seed[t],
+                                    (unsigned long long)p1, dbg ? dbg + 4 * (long long)t : nullptr);
+    if (threadIdx.x == 0) {
+        const long long nxt = bidx, n0 = n[t], n1 = n0 + 1;
+        tok[t] = nxt;
+        if (n0 >= 0 && n0 < out_cap) out[(long long)t * s_out + n0] = nxt;
+        n[t] = n1;
+        pos[t] = p1;
+        int reason = 0;
+        for (int j = 0; j < ns; ++j) reason |= (stop_ids[(long long)t * ns + j] == nxt) ? 1 : 0;
+        reason |= (n1 >= limit[t] ? 2 : 0) | (p1 >= Lc ? 4 : 0);
+        if (reason) { active[t] = 0; done[t] = (unsigned char)reason; }
+    }
+}
+
 // In-place rotary embedding of [rows, heads * 128] (a q or k projection output before the head transpose), HF rotate-half form with
 // the sign folded into `sin`: out[d] = round16(round16(x[d] * cos[d]) + x[d +- 64] * sin[d])  -- the rounding points of the stock
 // composition `torch.addcmul(x * cos, rot, sin)`, which costs five passes (cat, mul, addcmul + two temporaries) instead of one.

@@ -18,6 +18,7 @@ running the reference's modules under HF, all of them launch-count / traffic onl
     is captured once as a hipGraph and replayed: greedy feedback happens on the device, the host only polls the stop flags.
 """
 import math
+import operator
 import weakref
 
 import torch
@@ -969,9 +970,10 @@ class TenantDecoder(nn.Module):
         """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
-    def session(self, max_stop_ids=8):
-        """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step."""
-        return TenantSession(self, max_stop_ids)
+    def session(self, max_stop_ids=8, sampling=False):
+        """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
+        request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them."""
+        return TenantSession(self, max_stop_ids, sampling=sampling)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1020,6 +1022,37 @@ def extend_plan(pos, kv_start, done, n_tokens, Lc, active=False):
     return P, n
 
 
+def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    """The sampling parameters of one request, validated on the host: (temperature, top_k, top_p, seed) as (float, int, float, int).
+    temperature: finite and >= 0 (0 = greedy); top_k: an integer >= 0 (0 = off); top_p: 0 < top_p <= 1 (1 = off); seed: an integer in
+    [0, 2^64).  Anything else raises ValueError.  The defaults are greedy decoding."""
+    def integer(v, what):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            return operator.index(v)
+        except TypeError:
+            raise ValueError("%s = %r: an integer is required" % (what, v))
+    try:
+        tau, p = float(temperature), float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError("temperature = %r, top_p = %r: numbers are required" % (temperature, top_p))
+    if not (math.isfinite(tau) and tau >= 0.0):
+        raise ValueError("temperature = %r: a finite value >= 0 is required (0 = greedy)" % (temperature,))
+    k = integer(top_k, "top_k")
+    if k < 0:
+        raise ValueError("top_k = %r: an integer >= 0 is required (0 = off)" % (top_k,))
+    if not (0.0 < p <= 1.0):
+        raise ValueError("top_p = %r: 0 < top_p <= 1 is required (1 = off)" % (top_p,))
+    s_ = integer(seed, "seed")
+    if not (0 <= s_ < 1 << 64):
+        raise ValueError("seed = %r: 0 <= seed < 2^64 is required" % (seed,))
+    return tau, k, p, s_
+
+
+GREEDY = sampling_params()
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -1027,11 +1060,18 @@ class TenantSession:
     (serving_ops.step_begin_ragged / decode_attention_ragged / step_end_ragged): every tenant has its own pos / n / limit / active / done on the
     device.  An inactive tenant's row runs through the step as zeros and none of its state, cache rows or validity bytes is touched.
 
-    Greedy, one sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
+    sampling=True: a request carries temperature / top_k / top_p / seed (sampling_params; include/bitdelta_hip.h, bd_srv_sample_rows, defines the
+    token).  They are per-tenant device arrays next to pos / n / limit, written at admission and read by the launch that ends the step
+    (serving_ops.step_end_sample) -- never baked into the captured graph, so a tenant changes them from request to request without a new capture.
+    The draw index of a token is the cache row it will occupy: it rises through a conversation, extend included, so the same seed replays the same
+    conversation and no turn reuses the draws of the turn before; a caller who wants fresh randomness passes a new seed.  Without sampling=True the
+    session is greedy and refuses non-default sampling arguments (ValueError).
+
+    One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full; 0 = still active or never submitted."""
 
-    def __init__(self, dec, max_stop_ids=8):
+    def __init__(self, dec, max_stop_ids=8, sampling=False):
         _, _, _, heads, kvh, _ = dec.cfg
         if not (dec.fast_glue and dec.step_kernels):
             raise ValueError("a session runs on the HIP glue and step kernels (fast_glue, step_kernels); there is no stock-op ragged step")
@@ -1055,6 +1095,12 @@ class TenantSession:
         self.done = torch.zeros(T, dtype=torch.uint8, device=dev)
         self.stop_ids = torch.full((T, max(int(max_stop_ids), 1)), -1, dtype=torch.long, device=dev)
         self.out = torch.zeros(T, dec.max_len, dtype=torch.long, device=dev)      # (a caller may swap in a strided view BEFORE the first step)
+        self.sampling = bool(sampling)
+        if self.sampling:
+            self.temperature = torch.zeros(T, dtype=torch.float32, device=dev)
+            self.top_k = torch.zeros(T, dtype=torch.int32, device=dev)
+            self.top_p = torch.ones(T, dtype=torch.float32, device=dev)
+            self.seed = torch.zeros(T, dtype=torch.long, device=dev)          # the seed's 64 bits
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
         dec._sessions.add(self)
@@ -1076,7 +1122,47 @@ class TenantSession:
         self.done[t] = 0
         self.n[t] = 0
         self.out[t].zero_()
+        if self.sampling:
+            self._write_params(t, GREEDY)
         return rescaled
+
+    def _params(self, temperature, top_k, top_p, seed):
+        """one request's validated parameters; a session made without sampling=True takes the defaults only"""
+        sp = sampling_params(temperature, top_k, top_p, seed)
+        if not self.sampling and sp != GREEDY:
+            raise ValueError("this session is greedy: make it with session(sampling=True) to pass temperature / top_k / top_p / seed")
+        return sp
+
+    def _per_tenant(self, v):
+        if isinstance(v, torch.Tensor):
+            v = v.tolist()
+        if isinstance(v, (list, tuple)):
+            if len(v) != self.T:
+                raise ValueError("%d values for %d tenants" % (len(v), self.T))
+            return list(v)
+        return [v] * self.T
+
+    def _write_params(self, t, sp):
+        tau, k, p, s_ = sp
+        self.temperature[t] = tau
+        self.top_k[t] = min(k, 2 ** 31 - 1)
+        self.top_p[t] = p
+        self.seed[t] = s_ - (1 << 64) if s_ >= 1 << 63 else s_
+
+    def _first_tokens(self, logits, sps, d):
+        """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
+        cache row the token will occupy.  One host read, the one admission makes anyway."""
+        if not self.sampling:
+            return torch.argmax(logits, dim=-1).tolist()
+        dev = self.dec.dev
+        if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
+            logits = logits.contiguous()
+        tok = ops.sample_rows(logits, torch.tensor([sp[0] for sp in sps], dtype=torch.float32).to(dev),
+                              torch.tensor([min(sp[1], 2 ** 31 - 1) for sp in sps], dtype=torch.int32).to(dev),
+                              torch.tensor([sp[2] for sp in sps], dtype=torch.float32).to(dev),
+                              torch.tensor([sp[3] - (1 << 64) if sp[3] >= 1 << 63 else sp[3] for sp in sps], dtype=torch.long).to(dev),
+                              torch.full((len(sps),), int(d), dtype=torch.long).to(dev))
+        return tok.tolist()
 
     def _stops(self, stop_token_ids):
         s_ = sorted(int(i) for i in (stop_token_ids or ()))
@@ -1084,8 +1170,10 @@ class TenantSession:
             raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
         return s_
 
-    def _admit(self, t, first, L, max_new_tokens, stops):
-        """tenant t's state after its prefill: the first token is the prefill's argmax"""
+    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY):
+        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw)"""
+        if self.sampling:
+            self._write_params(t, sp)
         reason = (1 if first in stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
         self.stop_ids[t].fill_(-1)
         if stops:
@@ -1100,12 +1188,14 @@ class TenantSession:
         self.active_flags[t] = reason == 0
 
     @torch.no_grad()
-    def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=()):
+    def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
-        alone through tenant_view(t), and the tenant starts at its own position."""
+        alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
+        session(sampling=True); the first token's draw index is the padded length L."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
+        sp = self._params(temperature, top_k, top_p, seed)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
         L = padded_length(len(prompt))
@@ -1119,11 +1209,11 @@ class TenantSession:
         ids[0, L - len(prompt):] = torch.tensor(prompt, dtype=torch.long)
         am[0, L - len(prompt):] = True
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
-        self._admit(t, int(torch.argmax(logits, dim=-1)[0]), L, max_new_tokens, stops)
+        self._admit(t, int(self._first_tokens(logits, [sp], L)[0]), L, max_new_tokens, stops, sp)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
-    def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=()):
+    def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -1134,26 +1224,30 @@ class TenantSession:
         (ValueError).  Nobody else's state, cache rows or validity bytes are touched, and the captured step is reused.  One host read before the
         prefill (tenant t's activity flag, position, stop reason and last token together) and, as in submit, one of the first token after it.
         The conversation is the decoder's cache rows: a generate() on the decoder ends it
-        without the session knowing."""
+        without the session knowing.  temperature / top_k / top_p / seed as in submit (this turn's own; invalid ones raise ValueError before
+        anything is touched); the first token's draw index is P + n."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
         assert max_new_tokens >= 1
         tokens = [int(i) for i in tokens]
         stops = self._stops(stop_token_ids)
+        sp = self._params(temperature, top_k, top_p, seed)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
         ids = torch.tensor([[last] + tokens], dtype=torch.long).to(dec.dev)
         kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
-        self._admit(t, int(torch.argmax(logits, dim=-1)[0]), P + n, max_new_tokens, stops)
+        self._admit(t, int(self._first_tokens(logits, [sp], P + n)[0]), P + n, max_new_tokens, stops, sp)
 
     @torch.no_grad()
-    def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None):
+    def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
-        common padded length."""
+        common padded length.  temperature / top_k / top_p / seed: each a scalar or one value per tenant."""
         dec = self.dec
         assert max_new_tokens >= 1
+        sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
+                                             self._per_tenant(seed))]
         if bool(self.active_flags.any()):
             raise RuntimeError("a tenant is still generating")
         stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
@@ -1161,9 +1255,9 @@ class TenantSession:
         L = ids.shape[1]
         if L > self.Lc:
             raise ValueError("the padded prompts do not fit the KV cache")
-        first = torch.argmax(dec.prefill(ids, am, self.cache), dim=-1).tolist()
+        first = self._first_tokens(dec.prefill(ids, am, self.cache), sps, L)
         for t in range(self.T):
-            self._admit(t, first[t], L, max_new_tokens, stops[t])
+            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t])
             self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
@@ -1173,7 +1267,11 @@ class TenantSession:
         logits = dec.forward(self.tok, None, self.cache, None, x=x, ragged=(self.pos, self.active_flags))
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
             raise RuntimeError("the lm_head output is not laid out for the step kernel (16-byte aligned rows)")
-        ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
+        if self.sampling:
+            ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
+                                self.temperature, self.top_k, self.top_p, self.seed)
+        else:
+            ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
 
     def _state(self):
         return [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
@@ -1181,9 +1279,10 @@ class TenantSession:
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
-        alone."""
+        and the kind of session (greedy or sampling: another last launch) alone."""
         dec = self.dec
-        key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr())
+        key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
+               self.sampling)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:

@@ -272,6 +272,47 @@ def step_end_ragged(logits, tok, out, n, pos, limit, stop_ids, active, done, cac
                                            DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_end_ragged")
 
 
+def _sampling_arrays(R, temperature, top_k, top_p, seed, dbg):
+    assert temperature.dtype == torch.float32 and top_p.dtype == torch.float32 and top_k.dtype == torch.int32 and seed.dtype == torch.long
+    for v in (temperature, top_k, top_p, seed):
+        assert v.numel() == R and v.is_contiguous()
+    assert dbg is None or (dbg.dtype == torch.int32 and dbg.shape == (R, 4) and dbg.is_contiguous())
+
+
+def sample_rows(logits, temperature, top_k, top_p, seed, draw, dbg=None):
+    """One token per row of logits [R, V] (16-bit), each row with its own temperature / top_p (float32 [R]), top_k (int32 [R]), seed (int64 [R]:
+    the seed's 64 bits) and draw index `draw` (int64 [R]); include/bitdelta_hip.h (bd_srv_sample_rows) is the definition.  Returns tok, int64
+    [R].  dbg: an int32 [R, 4] tensor that receives kept count / smallest kept logit's bits / the token's Philox word / flags."""
+    require_gpu(logits, temperature, top_k, top_p, seed, draw, dbg)
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and draw.dtype == torch.long and draw.numel() == R and draw.is_contiguous()
+    _sampling_arrays(R, temperature, top_k, top_p, seed, dbg)
+    tok = torch.empty(R, dtype=torch.long, device=logits.device)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_sample_rows(ptr(logits), logits.stride(0), V, ptr(temperature), ptr(top_k), ptr(top_p), ptr(seed), ptr(draw), ptr(tok),
+                                       ptr(dbg), R, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_sample_rows")
+    return tok
+
+
+def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
+    """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
+    pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""
+    require_gpu(logits, tok, out, n, pos, limit, stop_ids, active, done, temperature, top_k, top_p, seed, dbg)
+    T, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and tok.dtype == torch.long and tok.is_contiguous() and tok.numel() == T
+    assert out.dtype == torch.long and out.shape[0] == T and out.stride(1) == 1 and stop_ids.dtype == torch.long and stop_ids.is_contiguous()
+    assert stop_ids.shape[0] == T and active.dtype == torch.bool and active.is_contiguous() and active.numel() == T
+    assert done.dtype == torch.uint8 and done.is_contiguous() and done.numel() == T
+    for v in (n, pos, limit):
+        assert v.dtype == torch.long and v.numel() == T and v.is_contiguous()
+    _sampling_arrays(T, temperature, top_k, top_p, seed, dbg)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_end_sample(ptr(logits), logits.stride(0), V, ptr(tok), ptr(out), out.stride(0), out.shape[1], ptr(stop_ids),
+                                           stop_ids.shape[1], ptr(pos), ptr(n), ptr(limit), ptr(active), ptr(done), int(cache_len),
+                                           ptr(temperature), ptr(top_k), ptr(top_p), ptr(seed), ptr(dbg), T, DTYPE_CODE[logits.dtype],
+                                           stream_ptr()), "srv_step_end_sample")
+
+
 def rope_kv_append_(qkv, cos, sin, kcache, vcache, heads, kvh, pos0=0):
     """Prefill from position pos0: rope_ on the q and k heads of the fused projection output qkv [T, S, (heads + 2 kvh) * 128] (in place) and, in the
     same launch, the rotated k rows and the v rows into the caches [T, kvh, Lc, 128] at positions pos0 .. pos0 + S - 1 (what

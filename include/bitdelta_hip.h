@@ -289,6 +289,40 @@ int bd_srv_step_begin_ragged(const void* embed, int64_t sEt, int64_t sEv, const 
 int bd_srv_step_end_ragged(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
                            const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done, int Lc, int T,
                            int dtype, void* stream);
+/* bd_srv_sample_rows / bd_srv_step_end_sample: a token chosen by temperature, top-k, top-p and a seed instead of argmax.  The token of a logits
+ * row is a PURE FUNCTION of the row and (tau, top_k, top_p, seed, d): it does not depend on the other rows of the launch, on graph or eager
+ * execution, or on thread order (every sum that decides a threshold is an integer sum; no floating-point atomics).  The definition:
+ *   Greedy: tau == 0 gives the token of bd_srv_step_end_ragged (torch.argmax's order).  A row that holds a NaN or +inf, or nothing finite, gives
+ *     that token whatever tau is.  -inf logits have weight 0 and are never sampled.  The token is always in [0, V).
+ *   Filters, in the order of HF's warpers (temperature, top-k, top-p), both on logit VALUES so that ties stay together (-0 == +0):
+ *     top-k (1 <= top_k < V): keep every token whose logit is >= the k-th largest logit (TopKLogitsWarper's `scores < topk(scores, k)[..., -1]`).
+ *     top-p (0 < top_p < 1): with w_i = exp((l_i - m) / tau) over the top-k survivors (m = the row's maximum) and Z = sum w_i, keep token i iff
+ *       sum_{l_j > l_i} w_j / Z < top_p -- the smallest set of highest values whose mass reaches top_p, all ties of the boundary value kept, at
+ *       least one token kept.  (TopPLogitsWarper keeps a sort-order-dependent subset of EQUAL boundary logits; this keeps all of them.)  The
+ *       masses are fp32 (hardware exp2) summed in 2^-40 fixed point: a row whose cumulative ratio lies within ~1e-5 of top_p may land on either
+ *       adjacent value.
+ *   Draw: Gumbel-max.  Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and counter = (i >> 2, 0, d & 0xffffffff, d >> 32); token i takes
+ *     output word r = word[i & 3]; u = ((r >> 8) + 0.5) * 2^-24; score_i = l_i / tau - log(-log u) in fp32 (-log u keeps its RELATIVE accuracy up to
+ *     u -> 1, where it is ~2^-25: from u = 1/2 on it is a series in the exact 1 - u); the token is the argmax of score_i over the kept set, ties to the lower index.
+ *   d is the draw index: the cache row the new token will occupy (bd_srv_step_end_sample: d = pos[t] + 1), so no two tokens of a conversation
+ *     share their draws; a caller who wants fresh randomness passes a new seed.
+ * Parameter VALUES are device data the host never sees.  The kernel neutralises what is out of range: tau < 0, NaN or +inf -> greedy;
+ *   top_k < 1 or >= V -> top-k off; top_p <= 0, >= 1 or NaN -> top-p off.
+ * bd_srv_sample_rows: R independent rows (logits [R, V] 16-bit, row stride sl), temperature / top_p float32 [R], top_k int32 [R], seed / draw
+ *   int64 [R] (the 64 bits of the seed; d), tok int64 [R] <- the tokens.  Nothing else is written.
+ * bd_srv_step_end_sample: bd_srv_step_end_ragged -- same state, same order of updates, same reasons, inactive tenants touch nothing -- with the
+ *   token chosen as above from temperature / top_k / top_p / seed [T] and d = pos[t] + 1.
+ * dbg (NULL in production): int32 [R or T, 4] <- the number of kept tokens, the 16-bit pattern of the smallest kept logit value (+0 for a zero),
+ *   the chosen token's Philox word r, flags (1 = the greedy rule decided -- the first three are then 0 --, 2 = top-k active, 4 = top-p active,
+ *   8 = the row held a NaN or +inf or nothing finite).  Rows of inactive tenants are not written.
+ * V % 8 == 0, sl % 8 == 0, sl >= V, logits 16-byte aligned, the parameter arrays naturally aligned; R == 0 / T == 0 is BD_OK and launches nothing.
+ * One 256-thread block per row; the row is read from global memory once per pass (argmax; two per active filter; the draw), any V. */
+int bd_srv_sample_rows(const void* logits, int64_t sl, int V, const float* temperature, const int32_t* top_k, const float* top_p,
+                       const int64_t* seed, const int64_t* draw, int64_t* tok, int32_t* dbg, int R, int dtype, void* stream);
+int bd_srv_step_end_sample(const void* logits, int64_t sl, int V, int64_t* tok, int64_t* out, int64_t s_out, int out_cap,
+                           const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done, int Lc,
+                           const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t* dbg, int T,
+                           int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
