@@ -17,6 +17,7 @@ DTYPE_CODE = {torch.float16: BD_F16, torch.bfloat16: BD_BF16, torch.float32: BD_
 WORD_DTYPE = {8: torch.uint8, 16: torch.int16, 32: torch.int32, 64: torch.int64}
 
 BD_DECODE_PLAN_INTS = 21          # include/bitdelta_hip_test.h: the record of bd_last_decode_plan
+BD_GEMM_PLAN_INTS = 49            # ... of bd_last_gemm_plan
 
 _i64, _vp, _ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
@@ -73,6 +74,8 @@ SIGNATURES = {
     "bd_tenant_signs_load": (_ci, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _ci, _ci, _i64, _i64, _i64, _vp]),
     "bd_set_gemm_variant": (_ci, [_ci]),
     "bd_last_gemm_variant": (_ci, []),
+    "bd_last_gemm_plan": (_ci, [ctypes.POINTER(ctypes.c_int32), _ci]),
+    "bd_set_gemm_dry_run": (_ci, [_ci]),
     "bd_set_tile_group_m": (_ci, [_ci]),
     "bd_set_launch_chunking": (_ci, [_ci]),
     "bd_set_tail_split": (_ci, [_ci]),

@@ -201,15 +201,14 @@ struct Problem {
     int64_t sNwNext;
     void* xw_out;
     const void* pn_w;         // bd_binary_linear_residual_norm: the RMSNorm that FOLLOWS this Linear -- weight [B or 1, N] (stride s_pnw), output pn_h
-    int64_t s_pnw;            // [B, M, N] (strides sHb / sHm).  A split-k reduce launch takes it along (splitk_reduce_norm_kernel) and sets
-    float pn_eps;             // t_post_norm_done; otherwise the entry point launches the norm after the Linear.
+    int64_t s_pnw;            // [B, M, N] (strides sHb / sHm).  A split-k reduce launch takes it along (splitk_reduce_norm_kernel; TilePlan::post_norm);
+    float pn_eps;             // otherwise the entry point launches the norm after the Linear.
     void* pn_h;
     int64_t sHb, sHm;
     void* ws;
     int64_t ws_bytes;
     hipStream_t st;
 };
-static thread_local int t_post_norm_done = 0;
 
 constexpr int MAX_DEVICES = 64;
 inline int current_device() {
@@ -870,108 +869,133 @@ int launch_gemv_chunk(const Problem& q, bool valu_form) {
 }
 
 
-inline GemmParams make_params(const Problem& q, int BM, int BN) {
-    GemmParams p;
-    p.A = (const char*)q.A; p.P = q.P; p.C = (char*)q.C; p.W = (const char*)q.W; p.alpha = q.alpha;
-    p.M = q.M; p.N = q.N; p.K = q.K;
-    p.tiles_m = (q.M + BM - 1) / BM; p.tiles_n = (q.N + BN - 1) / BN;
-    p.tile_m0 = 0; p.tile_n0 = 0; p.ksplit = 1;
-    p.sAb = q.sAb; p.sPb = q.sPb; p.sCb = q.sCb;
-    p.sAm = (int)q.sAm; p.sCm = (int)q.sCm; p.ldw = (int)q.ldw;
-    p.sAlb = (int)q.sAlb; p.gsz = q.N / q.G;
-    p.round_mode = q.round_mode; p.accumulate = q.accumulate;
-    p.nbatch = q.B; p.nent = q.B;
-    // Tile walk order (profiles/r01_tile_order.txt): delta-only = n fastest (the XCD's run shares X row panels; the mask is tiny).
-    // Fused = groups of 4 tile rows: each XCD's run covers a ~4 x 8 block of tiles, which minimises X + W bytes per XCD
-    // (+3..5 % on the MLP shapes over n-fastest, equal to m-fastest on the single-round ones).
-    p.group_m = q.W != nullptr ? (p.tiles_m < 4 ? p.tiles_m : 4) : 1;
-    if (g_forced_group_m > 0) p.group_m = g_forced_group_m < p.tiles_m ? g_forced_group_m : p.tiles_m;
-    return p;
+// ------------------------------------------------------------------ tile path: variants 0 - 21 and 100
+// Dispatched like the decode Linear: tile_plan() decides (plain host code: variant, k slices, tail split, workspace, every launch's tiles, grid
+// and LDS), TILE_ROWS says what each variant is and which calls it takes, and launch_tile_plan() lifts each planned launch to its Cfg type and
+// issues it through one body.  bd_last_gemm_plan reports the plan; under bd_set_gemm_dry_run nothing below dispatch() touches the device.
+
+// Schedules: 0 = single barrier per k-tile (bd_gemm_mfma.h; the small-M tiles), 1 = half-tile ping-pong (bd_gemm_pp.h), 2 = full-tile ping-pong
+// (bd_gemm_pf.h; the shipped delta-only schedule), 3 = one-pass fused, two accumulator sets (bd_gemm_fx.h), 4 = four-wave persistent
+// (bd_gemm_w4.h: grid = min(batch x tiles, CUs) workgroups of 256 threads, each walking its share of the (batch entry, tile) stream),
+// 5 = the generic edge kernel (bd_gemm_generic.h: any alignment, any K % 32 == 0).
+enum { S_SB = 0, S_PP = 1, S_PF = 2, S_FX = 3, S_W4 = 4, S_GEN = 5 };
+enum { FUSED_ONLY = 1, DELTA_ONLY = 2, EITHER = 3 };
+// W4Cfg OPT: LUT sign expansion (+1.5 % over VALU expansion, same box) + the k loop unrolled by four -- bit-identical outputs, -3.6 / -5.5 % cycles
+// per k-tile, +0.6 % on the timed prefill step in a same-box A/B of two library builds; profiles/r05_w4_cycles.txt
+constexpr int W4_OPT = 1 | 8192;
+
+// One row per tile variant (fused 0 / 5 have rows of their own: other schedules than the delta-only ones): id, the calls it serves, what it
+// takes (flags), schedule, tile rows x columns, wave rows, ring slots, the Cfg's OPT.
+enum {
+    T_F32 = 1,        // takes fp32 output
+    T_RESIDUAL = 2,   // takes a fused call's residual epilogue (Y += ...; one-pass fused tiles only)
+    T_SWIGLU = 4,     // requires Problem::epilogue == 1 (every other row requires 0)
+    T_AB = 8,         // a rejected schedule kept as an A/B reference: compiled only with -DBD_AB_VARIANTS (the native harness), the shipped
+                      // library answers BD_E_BAD_SHAPE
+    T_PAIR = 16,      // pair tiles: two batch entries of <= 64 rows share one 128 x 128 tile and its W stream
+    T_SPLIT = 32,     // k slices into fp32 slabs in the workspace + a reduce launch
+};
+struct TileRow {
+    int id, who, flags, sched, bm, bn, wm, ns, opt;
+    constexpr bool is(int flag) const { return (flags & flag) != 0; }
+};
+// The ORDER of the rows is the order in which the kernels are requested and so their order in the code object, which is worth time
+// (profiles/prefill_dispatch_refactor.txt): a new row goes where its kernel should lie, not where its number would sort.
+constexpr TileRow TILE_ROWS[] = {
+    {0, DELTA_ONLY, T_F32, S_PF, 256, 256, 2, 4, 1},                      // full-tile ping-pong, LUT sign expansion
+    {0, FUSED_ONLY, T_F32 | T_AB, S_PP, 256, 256, 2, 4, 2},               // two k loops over one accumulator set, 2-slot base ring
+    {5, DELTA_ONLY, T_F32, S_PF, 256, 128, 2, 4, 0},
+    {5, FUSED_ONLY, T_F32 | T_AB, S_PF, 256, 128, 2, 4, 0},
+    {6, EITHER, T_F32 | T_AB, S_PP, 256, 256, 2, 4, 2},                   // half-tile ping-pong (A/B reference)
+    {7, EITHER, T_F32 | T_AB, S_PP, 256, 128, 2, 4, 2},
+    {4, EITHER, T_F32 | T_AB, S_SB, 256, 256, 2, 4, 0},                   // single-barrier 256x256 (A/B reference)
+    {8, FUSED_ONLY, T_F32 | T_RESIDUAL, S_FX, 256, 128, 2, 3, 1},         // one-pass fused (profiles/r01_fx_vs_two_loop.txt)
+    // split-k over blockIdx.y + reduce launch (forced: k slices from the rule, at least 2): TWO rows, the 64x128 tile up to 64 rows per mask
+    // (half the MFMA / LDS work of a padded 128-row tile), then the 128x128 tile
+    {10, FUSED_ONLY, T_F32 | T_SPLIT, S_FX, 64, 128, 2, 4, 1},
+    {10, FUSED_ONLY, T_F32 | T_SPLIT, S_FX, 128, 128, 2, 4, 1},
+    // 64x128: up to 64 rows per mask (multi-tenant prefill of short prompts, demo_backend.py:297-299: M = 64 x 6 tenants) -- the 128-row
+    // tile does twice the MFMA and LDS work for rows that do not exist
+    {11, FUSED_ONLY, T_F32 | T_RESIDUAL, S_FX, 64, 128, 2, 4, 1},
+    {12, FUSED_ONLY, T_F32 | T_RESIDUAL, S_FX, 64, 256, 2, 3, 1},         // wide outputs / many tenants (see the rule)
+    {16, FUSED_ONLY, T_F32 | T_RESIDUAL | T_PAIR, S_FX, 128, 128, 2, 4, 1},              // pair tiles (multi-tenant prefill of short prompts)
+    {17, FUSED_ONLY, T_F32 | T_RESIDUAL | T_PAIR | T_SPLIT, S_FX, 128, 128, 2, 4, 1},    // ... + split-k (o / down of a 6-tenant request: 96 tiles on 256 CUs)
+    // FOUR-WAVE pair tiles: one wave per SIMD, wave tile 64 x 64, persistent over (pair, column tile); 21 = with the SwiGLU epilogue (gate|up of a
+    // multi-tenant request of short prompts, no [M, 2 I] round trip); 19 = + split-k: the stream runs over (pair, k slice, column tile), the
+    // slices are whole, equal runs of k-tiles, the residual is added by the reduce launch
+    {18, FUSED_ONLY, T_F32 | T_RESIDUAL | T_PAIR, S_W4, 128, 128, 2, 3, W4_OPT},
+    {21, FUSED_ONLY, T_SWIGLU | T_PAIR, S_W4, 128, 128, 2, 3, W4_OPT},
+    {20, FUSED_ONLY, T_F32 | T_RESIDUAL, S_W4, 128, 128, 2, 3, W4_OPT},   // ONE entry per tile (prompts of 65 .. 128 rows per tenant)
+    {19, FUSED_ONLY, T_F32 | T_RESIDUAL | T_PAIR | T_SPLIT, S_W4, 128, 128, 2, 3, W4_OPT},
+    {9, FUSED_ONLY, T_F32 | T_RESIDUAL, S_FX, 128, 128, 2, 4, 1},         // twice the tiles when 256x128 cannot fill the CUs (128 < M <~ 768)
+    {13, DELTA_ONLY, T_F32, S_W4, 256, 256, 2, 3, W4_OPT},
+    {14, FUSED_ONLY, T_F32 | T_RESIDUAL, S_W4, 256, 128, 2, 3, W4_OPT},   // (fp32 output: general-form epilogue only)
+    {15, FUSED_ONLY, T_SWIGLU, S_W4, 256, 128, 2, 3, W4_OPT},             // 14 with the SwiGLU epilogue (8-interleaved gate|up pair, C has N/2 columns)
+    {1, EITHER, T_F32, S_SB, 128, 256, 1, 4, 0},
+    {2, EITHER, T_F32, S_SB, 64, 256, 1, 4, 0},
+    {3, EITHER, T_F32, S_SB, 32, 256, 1, 4, 0},
+    {100, EITHER, T_F32, S_GEN, 64, 64, 1, 0, 0},
+};
+constexpr int N_TILE_ROWS = sizeof(TILE_ROWS) / sizeof(TILE_ROWS[0]);
+constexpr bool row_serves(const TileRow& r, bool fused) { return (r.who & (fused ? FUSED_ONLY : DELTA_ONLY)) && (STREAM_AB || !r.is(T_AB)); }
+// which launches of a row exist: fp32 ones where it takes fp32 output, and a split row's tile launch writes fp32 slabs whatever the output is
+constexpr bool row_launches(const TileRow& r, bool fused, bool f32) { return row_serves(r, fused) && (f32 ? r.is(T_F32) : !r.is(T_SPLIT)); }
+inline int tile_row(int id, bool fused) {
+    for (int i = 0; i < N_TILE_ROWS; ++i)
+        if (TILE_ROWS[i].id == id && row_serves(TILE_ROWS[i], fused)) return i;
+    return -1;
 }
 
+template <int DT_, bool FUSED_, bool OUT_F32_>
+struct GenericCfg {
+    static constexpr int DT = DT_, BM = 64, BN = 64, NT = 256, LDS_BYTES = 0;
+    static constexpr bool FUSED = FUSED_, OUT_F32 = OUT_F32_;
+};
+template <int I, int DT, bool FUSED, bool F32>
+struct RowCfg {
+    static constexpr TileRow r = TILE_ROWS[I];
+    static constexpr int epi = r.is(T_SWIGLU) ? 1 : 0, pair = r.is(T_PAIR) ? 1 : 0;
+    using type = std::conditional_t<r.sched == S_W4, W4Cfg<DT, r.bm, r.bn, FUSED, F32, r.opt, epi, pair>,
+                 std::conditional_t<r.sched == S_FX, FxCfg<DT, r.bm, r.bn, r.ns, F32, r.opt, pair>,
+                 std::conditional_t<r.sched == S_GEN, GenericCfg<DT, FUSED, F32>, GemmCfg<DT, r.bm, r.bn, r.wm, 4, r.ns, FUSED, F32, r.opt>>>>;
+};
 template <class Cfg, int SCHED> struct TileKernel { static auto get() { return delta_gemm_kernel<Cfg>; } };
 #ifdef BD_AB_VARIANTS
-template <class Cfg> struct TileKernel<Cfg, 1> { static auto get() { return delta_gemm_pp_kernel<Cfg>; } };
+template <class Cfg> struct TileKernel<Cfg, S_PP> { static auto get() { return delta_gemm_pp_kernel<Cfg>; } };
 #endif
-template <class Cfg> struct TileKernel<Cfg, 2> { static auto get() { return delta_gemm_pf_kernel<Cfg>; } };
-template <class Cfg> struct TileKernel<Cfg, 3> { static auto get() { return delta_gemm_fx_kernel<Cfg>; } };
+template <class Cfg> struct TileKernel<Cfg, S_PF> { static auto get() { return delta_gemm_pf_kernel<Cfg>; } };
+template <class Cfg> struct TileKernel<Cfg, S_FX> { static auto get() { return delta_gemm_fx_kernel<Cfg>; } };
+template <class Cfg> struct TileKernel<Cfg, S_W4> { static auto get() { return delta_gemm_w4_kernel<Cfg>; } };
+template <class Cfg> struct TileKernel<Cfg, S_GEN> { static auto get() { return delta_gemm_generic_kernel<Cfg::DT, Cfg::FUSED, Cfg::OUT_F32>; } };
 
-// SCHED 0 = single barrier per k-tile (bd_gemm_mfma.h; the small-M tiles), 1 = half-tile ping-pong (bd_gemm_pp.h),
-// 2 = full-tile ping-pong (bd_gemm_pf.h; the shipped delta-only schedule), 3 = one-pass fused, two accumulator sets (bd_gemm_fx.h).
-template <class Cfg, int SCHED = 0>
-int launch_tile(const Problem& q, int col0 = 0) {          // col0 > 0: only tile columns [col0, tiles_n) (launch_fused_tail_split)
-    GemmParams p = make_params(q, Cfg::BM, Cfg::BN);
-    if (col0 > 0) { p.tile_n0 = col0; p.tiles_n -= col0; if (p.tiles_n <= 0) return BD_OK; }
-    auto kern = TileKernel<Cfg, SCHED>::get();
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    // Experiment kept behind bd_set_launch_chunking(1): issue a multi-round problem as several launches of at most one tile per CU
-    // (an mc x nc block of tiles each, via GemmParams::tile_m0 / tile_n0).  Hypothesis: rounds inside one launch drift apart and that
-    // is why 8192x4096x4096 runs 10 % below back-to-back 2048-row launches.  Measured (profiles/r01_launch_chunking.txt): no gain
-    // (-0..3 %, -15 % with 6 tenants) -- the back-to-back figure was warm-cache re-reads of the same operands, not synchronisation.
-    const long long cus = num_cus();
-    const long long total = (long long)p.tiles_m * p.tiles_n * q.B;
-    if (SCHED >= 2 && g_launch_chunking && total > cus && q.B <= cus) {
-        const long long per = cus / q.B;                                   // tiles per launch and batch entry
-        // orientation A: all tile rows x as many tile columns as fit; B: all tile columns x as many rows as fit
-        long long mcA = p.tiles_m < per ? p.tiles_m : per, ncA = per / mcA; if (ncA > p.tiles_n) ncA = p.tiles_n;
-        long long ncB = p.tiles_n < per ? p.tiles_n : per, mcB = per / ncB; if (mcB > p.tiles_m) mcB = p.tiles_m;
-        const long long nA = ((p.tiles_m + mcA - 1) / mcA) * ((p.tiles_n + ncA - 1) / ncA);
-        const long long nB = ((p.tiles_m + mcB - 1) / mcB) * ((p.tiles_n + ncB - 1) / ncB);
-        const int mc = (int)(nA <= nB ? mcA : mcB), nc = (int)(nA <= nB ? ncA : ncB);
-        for (int m0 = 0; m0 < p.tiles_m; m0 += mc)
-            for (int n0 = 0; n0 < p.tiles_n; n0 += nc) {
-                GemmParams c = p;
-                c.tile_m0 = m0; c.tile_n0 = n0;
-                c.tiles_m = p.tiles_m - m0 < mc ? p.tiles_m - m0 : mc;
-                c.tiles_n = p.tiles_n - n0 < nc ? p.tiles_n - n0 : nc;
-                if (c.group_m > c.tiles_m) c.group_m = c.tiles_m;
-                dim3 grid((unsigned)(c.tiles_m * c.tiles_n), (unsigned)q.B);
-                hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, c);
-            }
-        return launch_status();
-    }
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)q.B);
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    return launch_status();
+// Lifts a row to its Cfg type and calls f(Tag<Cfg>, row index).  A launch the row does not have answers BD_E_BAD_SHAPE and instantiates nothing,
+// so exactly the table's kernels are compiled.  The launch record is read from the fp16 Cfg: block and LDS size do not depend on the dtype.
+template <class T> struct Tag { using type = T; };
+using TileRowSeq = std::make_integer_sequence<int, N_TILE_ROWS>;
+template <int DT, bool FUSED, bool F32, class F, int... Is>
+int lift_row(int row, F&& f, std::integer_sequence<int, Is...>) {
+    int rc = BD_E_BAD_SHAPE;
+    auto one = [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if constexpr (row_launches(TILE_ROWS[I], FUSED, F32)) {
+            using Cfg = typename RowCfg<I, DT, FUSED, F32>::type;
+            using Cfg16 = typename RowCfg<I, DT_F16, FUSED, F32>::type;
+            static_assert(Cfg::NT == Cfg16::NT && Cfg::LDS_BYTES == Cfg16::LDS_BYTES, "the plan records block and LDS bytes from the fp16 Cfg");
+            rc = f(Tag<Cfg>{}, i);
+        }
+    };
+    // (from the last row down: the compiler instantiates the bodies of `one` in the reverse of the order they are named here, and the order
+    //  of instantiation -- the table's -- is the order of the kernels in the code object)
+    (void)((row == N_TILE_ROWS - 1 - Is && (one(std::integral_constant<int, N_TILE_ROWS - 1 - Is>{}), true)) || ...);
+    return rc;
 }
 
-// Four-wave persistent kernels (bd_gemm_w4.h): grid = min(batch x tiles, CUs) workgroups of 256 threads, each walking its share of the
-// (batch entry, tile) stream.
-// cols >= 0: only tile columns [0, cols) of the problem (the rest goes to another launch: launch_fused_tail_split)
-// col0 > 0: only tile columns [col0, tiles_n) (the tail launch of launch_fused_tail_split)
-template <class Cfg>
-int launch_w4(const Problem& q, int cols = -1, int col0 = 0) {
-    GemmParams p = make_params(q, Cfg::BM, Cfg::BN);
-    if (cols >= 0) p.tiles_n = cols;
-    if (col0 > 0) { p.tile_n0 = col0; p.tiles_n -= col0; if (p.tiles_n <= 0) return BD_OK; }
-    auto kern = delta_gemm_w4_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    const long long total = (long long)p.tiles_m * p.tiles_n * q.B, cus = num_cus();
-    if (total <= 0) return BD_OK;
-    dim3 grid((unsigned)(total < cus ? total : cus));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    return launch_status();
-}
 // share of the CU-rounds a tile count keeps busy (1.0 = every round full)
-inline double round_fill(long long tiles) {
-    const long long cus = num_cus();
-    return (double)tiles / (double)(((tiles + cus - 1) / cus) * cus);
-}
-
-template <int DT, bool FUSED, bool OUT_F32>
-int launch_generic(const Problem& q) {
-    const GemmParams p = make_params(q, 64, 64);
-    dim3 grid((unsigned)((q.N + 63) / 64), (unsigned)((q.M + 63) / 64), (unsigned)q.B);
-    hipLaunchKernelGGL((delta_gemm_generic_kernel<DT, FUSED, OUT_F32>), grid, dim3(256), 0, q.st, p);
-    return launch_status();
-}
+inline double round_fill(long long tiles, long long cus) { return (double)tiles / (double)(((tiles + cus - 1) / cus) * cus); }
 
 // 256x256 vs 256x128 ping-pong tile: rounds of CU-wide tile waves x measured relative cost of one tile
 // (256x128 does half the work of a 256x256 tile at ~0.85x its MFMA rate; DESIGN.md "tile choice").
-inline int choose_big_tile(const Problem& q) {
-    const long long cus = num_cus();
+inline int choose_big_tile(const Problem& q, long long cus) {
     const long long tm = (q.M + 255) / 256;
     const long long t0 = tm * ((q.N + 255) / 256) * q.B, t5 = tm * ((q.N + 127) / 128) * q.B;
     const double c0 = (double)((t0 + cus - 1) / cus) * 1.0, c5 = (double)((t5 + cus - 1) / cus) * (0.5 / 0.85);
@@ -984,8 +1008,7 @@ inline int choose_big_tile(const Problem& q) {
 // (round 5: the 128x128 tile on the four-wave schedule, variant 20, takes ~0.64 of a four-wave 256x128 tile's k loop -- tools/ab_w4_128.py:
 //  M = 512 gate|up 3 rounds in 145.9 us vs 2 rounds in 149.9; M = 768 q|k|v 133.5 vs 138.7 -- and is 5..17 % faster than the 8-wave 128x128
 //  tile on every shape measured: profiles/r05_mt_prefill_tiles.txt)
-inline int choose_fused_tile(const Problem& q, double rel128 = 0.70) {
-    const long long cus = num_cus();
+inline int choose_fused_tile(const Problem& q, double rel128, long long cus) {
     const long long tn = (q.N + 127) / 128;
     const long long t8 = (q.M + 255) / 256 * tn * q.B, t9 = (q.M + 127) / 128 * tn * q.B;
     const double c8 = (double)((t8 + cus - 1) / cus), c9 = (double)((t9 + cus - 1) / cus) * rel128;
@@ -994,11 +1017,11 @@ inline int choose_fused_tile(const Problem& q, double rel128 = 0.70) {
 
 // Tail split of a multi-round fused launch (one mask, 16-bit output).  The persistent 256x128 kernel needs ceil(tiles / CUs) rounds; when
 // the last round is mostly empty (Llama-2-7B gate|up at 2048 rows: 1376 tiles = 5.4 rounds -> 6), the tile columns of the FULL rounds go
-// to it and the remaining columns to the 8-wave kernel on 128x128 tiles (twice as many, ~0.70 of a round each), launched behind it on
-// the same stream: 5 + 0.53 instead of 6 rounds.  Returns the number of 128-wide tile columns for the main launch, or -1 = no split.
-inline int fused_tail_split_cols(const Problem& q) {
+// to it and the remaining columns to 128x128 tiles (twice as many, ~0.70 of a round each), launched behind it on the same stream: 5 + 0.53
+// instead of 6 rounds.  The tail is four-wave since round 5 (variant 20's kernel: 5..17 % faster than the 8-wave 128x128 tile on every shape
+// measured); same 128-wide tile columns.  Returns the number of 128-wide tile columns for the main launch, or -1 = no split.
+inline int fused_tail_split_cols(const Problem& q, long long cus) {
     if (q.B != 1) return -1;
-    const long long cus = num_cus();
     const long long tm = (q.M + 255) / 256, tn = (q.N + 127) / 128, T = tm * tn;
     if (T <= cus || T % cus == 0) return -1;
     const long long full = T / cus;                       // full rounds
@@ -1015,9 +1038,8 @@ inline int fused_tail_split_cols(const Problem& q) {
 // even 128x128 tiles leave most CUs idle and the launch is bound by how fast FEW CUs can stream W.  KS slices of k per tile (each
 // block writes an fp32 partial [M][N] slab to the workspace) + one reduce launch.  Returns KS (1 = do not split).
 constexpr int64_t SPLITK_WS_CAP = 64ll << 20;
-inline int splitk_factor(int B, int M, int N, int K) {
+inline int splitk_factor(int B, int M, int N, int K, long long cus) {
     if (M <= 16 || M > 512 || K % 64 || N % 8) return 1;
-    const long long cus = num_cus();
     const long long tiles = (long long)((M + 127) / 128) * ((N + 127) / 128) * B;
     if (tiles * 2 > cus) return 1;                       // already at least half a round of tiles
     long long ks = cus / tiles;
@@ -1028,54 +1050,12 @@ inline int splitk_factor(int B, int M, int N, int K) {
     return ks < 2 ? 1 : (int)ks;
 }
 
-// the reduce launch of the split-k tile kernels: partial slabs [B][KS][M][N] -> C.  A pending post-norm (Problem::pn_w) rides on it when the rows
-// are whole 16-byte chunks of at most 8192 columns: one launch instead of reduce + RMSNorm.
-template <int DT>
-inline void launch_splitk_reduce(const Problem& q, const float* part, int KS, int accumulate) {
-    if (q.pn_w && q.out_dtype != BD_F32 && q.N % 8 == 0 && q.N <= 8192 && aligned16(q.C) && q.sCm % 8 == 0 && q.sCb % 8 == 0) {
-        hipLaunchKernelGGL((splitk_reduce_norm_kernel<DT>), dim3((unsigned)(q.B * q.M)), dim3(256), 0, q.st, part, (unsigned short*)q.C,
-                           (const unsigned short*)q.pn_w, (unsigned short*)q.pn_h, KS, q.M, q.N, (long long)q.sCb, (long long)q.sCm,
-                           (long long)q.sHb, (long long)q.sHm, (long long)q.s_pnw, accumulate, q.pn_eps);
-        t_post_norm_done = 1;
-        return;
-    }
-    const long long per = (long long)q.M * q.N / 4;
-    dim3 g2((unsigned)((per + 255) / 256), (unsigned)q.B);
-    hipLaunchKernelGGL((splitk_reduce_kernel<DT>), g2, dim3(256), 0, q.st, part, q.C, q.B, KS, q.M, q.N,
-                       (long long)q.sCb, (int)q.sCm, q.out_dtype == BD_F32 ? 1 : 0, accumulate);
-}
-
-template <int DT, int BM>
-int launch_fused_splitk_bm(const Problem& q, int KS) {
-    const int64_t need = GEMV_TICKET_BYTES + (int64_t)q.B * KS * q.M * q.N * 4;
-    if (!q.ws || q.ws_bytes < need) return BD_E_WORKSPACE;
-    float* part = (float*)((char*)q.ws + GEMV_TICKET_BYTES);
-    Problem c = q;
-    c.C = part; c.out_dtype = BD_F32; c.sCm = q.N; c.sCb = (int64_t)q.M * q.N;     // slab y = b * KS + ks
-    using Cfg = FxCfg<DT, BM, 128, 4, true, 1>;
-    GemmParams p = make_params(c, Cfg::BM, Cfg::BN);
-    p.ksplit = KS;
-    auto kern = delta_gemm_fx_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(q.B * KS));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    launch_splitk_reduce<DT>(q, part, KS, 0);
-    return launch_status();
-}
-// up to 64 rows per mask: 64-row tiles (half the MFMA / LDS work of a padded 128-row tile)
-template <int DT>
-int launch_fused_splitk(const Problem& q, int KS) {
-    return q.M <= 64 ? launch_fused_splitk_bm<DT, 64>(q, KS) : launch_fused_splitk_bm<DT, 128>(q, KS);
-}
-
-// ---- pair tiles (bd_gemm_fx.h, PAIR): two batch entries of <= 64 rows share one 128 x 128 tile (and its W stream); optional split-k
+// ---- pair tiles (bd_gemm_fx.h / bd_gemm_w4.h, PAIR): two batch entries of <= 64 rows share one 128 x 128 tile (and its W stream); optional split-k
 inline bool pair_ok(const Problem& q) {
     return q.W && q.B >= 2 && q.M >= 1 && q.M <= 64 && fast_ok(q) && q.sAb >= 0 && q.sAb < (1ll << 30) && q.sPb >= 0 && q.sPb < (1ll << 29);
 }
 static const int g_pair_ks_env = env_int("BD_PAIR_SPLITK", 0);       // A/B: force the k-slice count of the split pair tiles (0 = the rule)
-inline int pair_splitk_dims(int B, int N, int K) {    // k slices so that pairs x column tiles x slices ~ fills the CUs (>= 512 k per slice)
-    const long long cus = num_cus();
+inline int pair_splitk_dims(int B, int N, int K, long long cus) {    // k slices so that pairs x column tiles x slices ~ fills the CUs (>= 512 k per slice)
     const long long tiles = (long long)((B + 1) / 2) * ((N + 127) / 128);
     if (K % 64 || N % 8 || tiles * 2 > cus) return 1;
     if (g_pair_ks_env > 1) { int f = g_pair_ks_env; while (f > 1 && (K / f < 512 || (K / 64) % f)) --f; return f; }
@@ -1084,80 +1064,61 @@ inline int pair_splitk_dims(int B, int N, int K) {    // k slices so that pairs 
     while (ks > 1 && K / ks < 512) --ks;
     return (int)ks;
 }
-inline int pair_splitk(const Problem& q) { return pair_splitk_dims(q.B, q.N, q.K); }
-template <int DT, bool OUT_F32>
-int launch_pair(const Problem& q) {
-    using Cfg = FxCfg<DT, 128, 128, 4, OUT_F32, 1, 1>;
-    GemmParams p = make_params(q, Cfg::BM, Cfg::BN);          // tiles_m = 1: the tile's two halves are two batch entries
-    auto kern = delta_gemm_fx_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)((q.B + 1) / 2));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    return launch_status();
-}
-template <int DT>
-int launch_pair_splitk(const Problem& q, int KS) {
-    const int64_t need = GEMV_TICKET_BYTES + (int64_t)q.B * KS * q.M * q.N * 4;
-    if (!q.ws || q.ws_bytes < need) return BD_E_WORKSPACE;
-    float* part = (float*)((char*)q.ws + GEMV_TICKET_BYTES);
-    Problem c = q;
-    c.C = part; c.out_dtype = BD_F32; c.sCm = q.N; c.sCb = (int64_t)q.M * q.N;     // slab y = entry * KS + ks
-    c.accumulate = 0;                                                                // (the residual is added by the reduce launch)
-    using Cfg = FxCfg<DT, 128, 128, 4, true, 1, 1>;
-    GemmParams p = make_params(c, Cfg::BM, Cfg::BN);
-    p.ksplit = KS;
-    auto kern = delta_gemm_fx_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(((q.B + 1) / 2) * KS));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    launch_splitk_reduce<DT>(q, part, KS, q.accumulate);
-    return launch_status();
+
+// One launch of a tile plan; bd_last_gemm_plan reports it field by field.
+struct TileLaunch {
+    bool on = false;                   // issued at all
+    int row = -1, f32 = 0;             // the kernel: TILE_ROWS index, and whether THIS launch writes fp32 (the output itself or split-k slabs)
+    int bm = 0, bn = 0, sched = 0;     // (reduce launch: sched 1 = it carries the post-norm)
+    int tiles_m = 0, tiles_n = 0, tile_n0 = 0, group_m = 0, ksplit = 0, nbatch = 0, nent = 0;      // GemmParams
+    unsigned grid_x = 0, grid_y = 0;   // (generic kernel: z = nbatch)
+    int block = 0, lds = 0;            // threads per block, dynamic LDS bytes
+};
+// What tile_plan decides about one call.
+struct TilePlan {
+    int rc = BD_OK;                    // != BD_OK: the call is refused
+    int variant = -1;                  // bd_last_gemm_variant (>= 200: a decode family; nothing below is filled)
+    int ks = 1, tail_col = -1;         // k slices (1 = unsplit); first 128-wide tile column of variant 14's tail launch (-1 = none)
+    int64_t ws_bytes = 0;              // workspace the plan needs
+    int post_norm = 0;                 // the reduce launch carries Problem::pn_w (otherwise the entry point launches the norm after the Linear)
+    bool chunked = false;              // bd_set_launch_chunking applies to the main launch (not part of the record)
+    TileLaunch main, tail, reduce;
+};
+static thread_local TilePlan t_tile_plan;           // of this thread's last call that reached dispatch()
+static thread_local int g_gemm_dry_run = 0;         // bd_set_gemm_dry_run: plan and record, never touch the device
+
+inline int64_t slab_bytes(const Problem& q, int ks) { return GEMV_TICKET_BYTES + (int64_t)q.B * ks * q.M * q.N * 4; }
+
+// the launch of row `ri` over tile columns [col0, col1) of the problem (col1 < 0: to the last one)
+inline TileLaunch plan_launch(const Problem& q, int ri, bool fused, bool f32, int ks, int col0, int col1, long long cus) {
+    const TileRow& r = TILE_ROWS[ri];
+    TileLaunch l;
+    l.on = true; l.row = ri; l.f32 = f32; l.bm = r.bm; l.bn = r.bn; l.sched = r.sched;
+    l.tiles_m = (q.M + r.bm - 1) / r.bm;
+    l.tile_n0 = col0; l.tiles_n = (col1 < 0 ? (q.N + r.bn - 1) / r.bn : col1) - col0;
+    l.ksplit = ks;
+    const int entries = r.is(T_PAIR) ? (q.B + 1) / 2 : q.B;          // a pair tile's two halves are two batch entries (tiles_m = 1)
+    l.nent = q.B; l.nbatch = r.sched == S_W4 ? entries * ks : q.B;
+    // Tile walk order (profiles/r01_tile_order.txt): delta-only = n fastest (the XCD's run shares X row panels; the mask is tiny).
+    // Fused = groups of 4 tile rows: each XCD's run covers a ~4 x 8 block of tiles, which minimises X + W bytes per XCD
+    // (+3..5 % on the MLP shapes over n-fastest, equal to m-fastest on the single-round ones).
+    l.group_m = fused ? (l.tiles_m < 4 ? l.tiles_m : 4) : 1;
+    if (g_forced_group_m > 0) l.group_m = g_forced_group_m < l.tiles_m ? g_forced_group_m : l.tiles_m;
+    const long long total = (long long)l.tiles_m * l.tiles_n * l.nbatch;
+    if (r.sched == S_W4) { l.grid_x = (unsigned)(total < cus ? total : cus); l.grid_y = 1; }
+    else if (r.sched == S_GEN) { l.grid_x = (unsigned)l.tiles_n; l.grid_y = (unsigned)l.tiles_m; }
+    else { l.grid_x = (unsigned)(l.tiles_m * l.tiles_n); l.grid_y = (unsigned)(entries * ks); }
+    const auto geometry = [&](auto tag, auto) { using Cfg = typename decltype(tag)::type; l.block = Cfg::NT; l.lds = Cfg::LDS_BYTES; return BD_OK; };
+    if (fused) f32 ? lift_row<DT_F16, true, true>(ri, geometry, TileRowSeq{}) : lift_row<DT_F16, true, false>(ri, geometry, TileRowSeq{});
+    else f32 ? lift_row<DT_F16, false, true>(ri, geometry, TileRowSeq{}) : lift_row<DT_F16, false, false>(ri, geometry, TileRowSeq{});
+    return l;
 }
 
-// four-wave PAIR tiles (W4Cfg PAIR = 1): two batch entries of <= 64 rows per 128 x 128 tile, persistent over (pair, column tile)
-template <int DT, bool OUT_F32, int EPI = 0>
-int launch_w4_pair(const Problem& q) {
-    using Cfg = W4Cfg<DT, 128, 128, true, OUT_F32, 1 | 8192, EPI, 1>;
-    GemmParams p = make_params(q, Cfg::BM, Cfg::BN);          // tiles_m = 1: the tile's two wave rows are two batch entries
-    p.nent = q.B; p.nbatch = (q.B + 1) / 2;
-    auto kern = delta_gemm_w4_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    const long long total = (long long)p.tiles_n * p.nbatch, cus = num_cus();
-    if (total <= 0) return BD_OK;
-    dim3 grid((unsigned)(total < cus ? total : cus));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    return launch_status();
-}
-// ... + split-k: the persistent stream runs over (pair, k slice, column tile); fp32 partial slabs [entry * KS + slice][M][N], then the reduce launch
-// of launch_pair_splitk (residual added there).  KS must divide the k-tile count.
-template <int DT>
-int launch_w4_pair_splitk(const Problem& q, int KS) {
-    const int64_t need = GEMV_TICKET_BYTES + (int64_t)q.B * KS * q.M * q.N * 4;
-    if (!q.ws || q.ws_bytes < need) return BD_E_WORKSPACE;
-    if ((q.K / 64) % KS) return BD_E_BAD_SHAPE;
-    float* part = (float*)((char*)q.ws + GEMV_TICKET_BYTES);
-    Problem c = q;
-    c.C = part; c.out_dtype = BD_F32; c.sCm = q.N; c.sCb = (int64_t)q.M * q.N;     // slab = entry * KS + slice
-    c.accumulate = 0;
-    using Cfg = W4Cfg<DT, 128, 128, true, true, 1 | 8192, 0, 1>;
-    GemmParams p = make_params(c, Cfg::BM, Cfg::BN);
-    p.ksplit = KS; p.nent = q.B; p.nbatch = ((q.B + 1) / 2) * KS;
-    auto kern = delta_gemm_w4_kernel<Cfg>;
-    static std::atomic<uint64_t> lds_done{0};
-    if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
-    const long long total = (long long)p.tiles_n * p.nbatch, cus = num_cus();
-    dim3 grid((unsigned)(total < cus ? total : cus));
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::LDS_BYTES, q.st, p);
-    launch_splitk_reduce<DT>(q, part, KS, q.accumulate);
-    return launch_status();
-}
-
-template <int DT, bool FUSED, bool OUT_F32>
-int dispatch3(const Problem& q) {
+// fills `pl` (a fresh TilePlan)
+void tile_plan(const Problem& q, bool fused, bool out_f32, long long cus, TilePlan& pl) {
+    const auto refuse = [&](int rc) { pl.rc = rc; };
     int v = g_forced_variant;
+    const bool forced = v >= 0;
     if (v > 200 && v <= 264) v = 200;        // 200 + KS: decode path with a forced k-split (test hook)
     if (v > 300 && v <= 364) v = 300;        // 300 (+ KS): force the VALU sign-flip decode kernel
     if (v > 400 && v <= 464) v = 400;        // 400 (+ KS): force the MFMA + LUT decode kernel
@@ -1165,164 +1126,173 @@ int dispatch3(const Problem& q) {
     if (v > 600 && v <= 664) v = 600;        // 600 (+ columns per block / 4): force the streaming decode kernel
     if (v > 800 && v <= 804) v = 800;        // 800 (+ masks per block): force the one-mask-per-row delta kernel (bd_gemv_rows.h)
     if (v == 700) {                           // 700: the loader / consumer decode kernel (packed sign layout, fused Linear only); the
-        if (q.mask_tiled != 2 || !q.W) return BD_E_BAD_SHAPE;     // stream path picks it up (launch_gemv_stream_chunk, ring_wanted)
+        if (q.mask_tiled != 2 || !q.W) return refuse(BD_E_BAD_SHAPE);     // stream path picks it up (launch_gemv_stream_chunk, ring_wanted)
         v = 600;
     }
-    if (q.epilogue == 1 && q.M > GEMV_MAX_M) {        // prefill-size SwiGLU launch (bd_binary_linear_swiglu): the four-wave kernel's 256 x 128 tile,
-        if (v >= 0 && v != 15 && v != 21) return BD_E_BAD_SHAPE;                  // or its pair tile for several entries of <= 64 rows (round 6)
-        if (v < 0) v = (FUSED && q.M <= 64 && q.B >= 2 && pair_ok(q)) ? 21 : 15;
+    // prefill-size SwiGLU launch (bd_binary_linear_swiglu): the four-wave kernel's 256 x 128 tile, or its pair tile for several entries of <= 64
+    // rows (round 6) -- the rows with epi = 1
+    const bool swiglu = q.epilogue == 1 && q.M > GEMV_MAX_M;
+    const auto slices = [&](bool pair) { return pair ? pair_splitk_dims(q.B, q.N, q.K, cus) : splitk_factor(q.B, q.M, q.N, q.K, cus); };
+    const auto ws_holds = [&](int ks) { return q.ws && q.ws_bytes >= slab_bytes(q, ks); };
+    const bool slab_rows = q.N % 8 == 0 && q.sCm % 4 == 0 && q.sCb % 4 == 0;          // the reduce launch reads and writes whole 16-byte chunks
+    int ks = 1;
+    const auto split10 = [&](int& n) { n = slices(false); return n > 1 && ws_holds(n); };      // the unpaired split: its slice count, and whether it is taken
+    if (forced) {
+        if (swiglu && v >= 200) return refuse(BD_E_BAD_SHAPE);
+        if ((v == 200 || v == 300 || v == 400 || v == 500 || v == 600) && !gemv_ok(q)) return refuse(BD_E_BAD_SHAPE);
+    } else if (swiglu) v = (fused && q.M <= 64 && q.B >= 2 && pair_ok(q)) ? 21 : 15;
+    else if (gemv_ok(q)) v = 200;
+    else if (!fast_ok(q)) v = 100;
+    else if (fused && q.M > 16 && q.M <= 64 && q.B >= 2 && pair_ok(q)) {
+        // several batch entries of <= 64 rows (multi-tenant prefill of short prompts, demo_backend.py:297-299): two entries per 128-row
+        // tile share one W stream; narrow outputs add split-k (tools/bench_mt_prefill.py, 6 tenants x 64 rows, Mistral-7B shapes:
+        // q|k|v 59 -> 50 us, o 39 -> 33, gate|up 201 -> 177, down 130 -> 91; profiles/r04_mt_prefill_tiles.txt)
+        // Round 5: the same tiles on the FOUR-WAVE schedule (bd_gemm_w4.h PAIR; variants 18 / 19) -- q|k|v 51.6 -> 51.4 us, o 35.3 -> 32.2,
+        // gate|up 192 -> 162 (1.12 PF useful), down 94.6 -> 83.4: -12 % per layer (profiles/r05_mt_prefill_tiles.txt).  Its split-k
+        // slices are whole runs of k-tiles: when the slice count does not divide K / 64 the 8-wave kernel keeps the launch.
+        // (A workspace that is missing or too small silently keeps the unsplit launch.)
+        ks = slices(true);
+        const bool split = ks > 1 && slab_rows && ws_holds(ks);
+        if (!split) v = 18;
+        else v = (q.K / 64) % ks == 0 ? 19 : 17;
     }
-    if (v < 0) {
-        if (gemv_ok(q)) v = 200;
-        else if (!fast_ok(q)) v = 100;
-        else if (FUSED && q.M > 16 && q.M <= 64 && q.B >= 2 && pair_ok(q)) {
-            // several batch entries of <= 64 rows (multi-tenant prefill of short prompts, demo_backend.py:297-299): two entries per 128-row
-            // tile share one W stream; narrow outputs add split-k (tools/bench_mt_prefill.py, 6 tenants x 64 rows, Mistral-7B shapes:
-            // q|k|v 59 -> 50 us, o 39 -> 33, gate|up 201 -> 177, down 130 -> 91; profiles/r04_mt_prefill_tiles.txt)
-            // Round 5: the same tiles on the FOUR-WAVE schedule (bd_gemm_w4.h PAIR; variants 18 / 19) -- q|k|v 51.6 -> 51.4 us, o 35.3 -> 32.2,
-            // gate|up 192 -> 162 (1.12 PF useful), down 94.6 -> 83.4: -12 % per layer (profiles/r05_mt_prefill_tiles.txt).  Its split-k
-            // slices are whole runs of k-tiles: when the slice count does not divide K / 64 the 8-wave kernel keeps the launch.
-            const int kp = pair_splitk(q);
-            const bool split = kp > 1 && q.N % 8 == 0 && q.sCm % 4 == 0 && q.sCb % 4 == 0 && q.ws &&
-                               q.ws_bytes >= GEMV_TICKET_BYTES + (int64_t)q.B * kp * q.M * q.N * 4;
-            v = split ? (((q.K / 64) % kp == 0) ? 19 : 17) : 18;
-        }
-        else if (FUSED && q.M > 16 && !q.accumulate && q.sCm % 4 == 0 && q.sCb % 4 == 0 && splitk_factor(q.B, q.M, q.N, q.K) > 1 && q.ws &&
-                 q.ws_bytes >= GEMV_TICKET_BYTES + (int64_t)q.B * splitk_factor(q.B, q.M, q.N, q.K) * q.M * q.N * 4) v = 10;
-        else if (FUSED && q.M > 16 && q.M <= 64)                  // (not split: there are enough 64-row tiles)
-            // 64x256 tiles (twice the MFMAs per X fragment read) once they fill at least half the CUs, else 64x128 for the parallelism:
-            // 6 tenants x 64 rows: q+k+v 56 vs 76 us, gate+up 207 vs 253 us, but o 54 vs 38 us (tools/bench_mt_prefill.py)
-            v = ((long long)((q.N + 255) / 256) * q.B * 2 >= num_cus()) ? 12 : 11;
-        else if (FUSED && q.M > 16) {
-            v = choose_fused_tile(q, OUT_F32 ? 0.70 : 0.64);     // fused: one-pass kernel (profiles/r01_fx_vs_two_loop.txt, r01_small_m.txt,
-                                          // r01_mid_m.txt: also for 16 < M <= 64, rows padded to the 128-row tile)
-            // same tiles on the four-wave persistent schedule: 256x128 +4..7 % on every shape measured (profiles/r03_w4_*.txt), 128x128
-            // +5..17 % (round 5)
-            if (v == 8 && !OUT_F32) v = 14;
-            if (v == 9 && !OUT_F32) v = 20;
-        } else if (q.M > 128) {
-            v = choose_big_tile(q);
-            // four-wave persistent 256x256 kernel once its tiles keep >= 80 % of the CU-rounds busy (it has no 256x128 form)
-            if (round_fill((long long)((q.M + 255) / 256) * ((q.N + 255) / 256) * q.B) >= 0.8) v = 13;
-        }
-        else if (q.M > 64) v = 1;
-        else if (q.M > 32) v = 2;
-        else v = 3;
-    } else {
-        if ((v == 200 || v == 300 || v == 400 || v == 500 || v == 600) && !gemv_ok(q)) return BD_E_BAD_SHAPE;
-        if (v >= 0 && v <= 20 && !fast_ok(q)) return BD_E_BAD_SHAPE;
-        if ((v == 16 || v == 17 || v == 18 || v == 19 || v == 20) && !FUSED) return BD_E_BAD_SHAPE;
-        if (v == 15 && (!FUSED || OUT_F32 || q.epilogue != 1)) return BD_E_BAD_SHAPE;
-        if (v == 13 && FUSED) return BD_E_BAD_SHAPE;
-        if (v == 14 && !FUSED) return BD_E_BAD_SHAPE;
-        if ((v == 8 || v == 9 || v == 10 || v == 11 || v == 12) && !FUSED) return BD_E_BAD_SHAPE;
-        if (v == 10 && (q.N % 8 || q.sCm % 4 || q.sCb % 4 || q.accumulate)) return BD_E_BAD_SHAPE;
-        if (FUSED && q.accumulate && !(v == 8 || v == 9 || v == 11 || v == 12 || v == 14 || v == 16 || v == 17 || v == 18 || v == 19 || v == 20 || v == 200 || v == 300 || v == 400 || v == 500 || v == 600))
-            return BD_E_BAD_SHAPE;            // residual epilogue: one-pass fused tiles and the decode kernels only
+    else if (fused && q.M > 16 && !q.accumulate && slab_rows && split10(ks)) v = 10;
+    else if (fused && q.M > 16 && q.M <= 64)                  // (not split: there are enough 64-row tiles)
+        // 64x256 tiles (twice the MFMAs per X fragment read) once they fill at least half the CUs, else 64x128 for the parallelism:
+        // 6 tenants x 64 rows: q+k+v 56 vs 76 us, gate+up 207 vs 253 us, but o 54 vs 38 us (tools/bench_mt_prefill.py)
+        v = ((long long)((q.N + 255) / 256) * q.B * 2 >= cus) ? 12 : 11;
+    else if (fused && q.M > 16) {
+        // one-pass kernel (profiles/r01_fx_vs_two_loop.txt, r01_small_m.txt, r01_mid_m.txt: also for 16 < M <= 64, rows padded to the 128-row
+        // tile); 16-bit outputs: the same tiles on the four-wave persistent schedule: 256x128 +4..7 % on every shape measured
+        // (profiles/r03_w4_*.txt), 128x128 +5..17 % (round 5)
+        v = choose_fused_tile(q, out_f32 ? 0.70 : 0.64, cus);
+        if (!out_f32) v = v == 8 ? 14 : 20;
+    } else if (q.M > 128) {
+        v = choose_big_tile(q, cus);
+        // four-wave persistent 256x256 kernel once its tiles keep >= 80 % of the CU-rounds busy (it has no 256x128 form)
+        if (round_fill((long long)((q.M + 255) / 256) * ((q.N + 255) / 256) * q.B, cus) >= 0.8) v = 13;
     }
-    t_last_variant = v;
+    else v = q.M > 64 ? 1 : q.M > 32 ? 2 : 3;
+    if (v >= 200) { pl.variant = v; return; }              // a decode family: dispatch_decode
+    // what the variant takes (a forced variant whose preconditions fail is refused, never replaced)
+    const int ri = tile_row(v, fused);
+    if (ri < 0) return refuse(BD_E_BAD_SHAPE);
+    const TileRow& r = TILE_ROWS[ri];
+    const bool split = r.is(T_SPLIT), pair = r.is(T_PAIR);
+    if ((r.sched != S_GEN && !fast_ok(q)) || (out_f32 && !r.is(T_F32)) || r.is(T_SWIGLU) != swiglu || (fused && q.accumulate && !r.is(T_RESIDUAL)) ||
+        (split && !slab_rows))
+        return refuse(BD_E_BAD_SHAPE);
+    pl.variant = v;                       // (as before the plan: the refusals below leave the variant they refused in bd_last_gemm_variant)
+    if (pair && !pair_ok(q)) return refuse(BD_E_BAD_SHAPE);
+    if (split) {
+        if (forced) {                     // k slices from the rule, at least 2; 19: whole, equal runs of k-tiles; every slice holds a 64-k tile
+            ks = slices(pair);
+            if (ks < 2) ks = (v == 19 || q.K / 64 >= 2) ? 2 : 1;
+            while (v == 19 && ks > 1 && (q.K / 64) % ks) --ks;
+            if (ks < 2 || ks > q.K / 64) return refuse(BD_E_BAD_SHAPE);
+        }
+        pl.ks = ks; pl.ws_bytes = slab_bytes(q, ks);
+        if (!ws_holds(ks)) return refuse(BD_E_WORKSPACE);
+    }
+    if (v == 14 && !forced && g_tail_split && !out_f32) pl.tail_col = fused_tail_split_cols(q, cus);
+    pl.main = plan_launch(q, v == 10 && q.M > 64 ? ri + 1 : ri, fused, split || out_f32, pl.ks, 0, pl.tail_col, cus);      // (10's second row)
+    if (pl.tail_col >= 0) pl.tail = plan_launch(q, tile_row(20, true), true, false, 1, pl.tail_col, -1, cus);
+    pl.chunked = g_launch_chunking && (r.sched == S_PF || r.sched == S_FX) && !pair && !split;
+    if (split) {
+        // partial slabs [B][KS][M][N] -> C.  A pending post-norm (Problem::pn_w) rides on the reduce launch when the rows are whole 16-byte
+        // chunks of at most 8192 columns: one launch instead of reduce + RMSNorm.
+        TileLaunch& d = pl.reduce;
+        pl.post_norm = q.pn_w && !out_f32 && q.N % 8 == 0 && q.N <= 8192 && aligned16(q.C) && q.sCm % 8 == 0 && q.sCb % 8 == 0;
+        d.on = true; d.sched = pl.post_norm; d.ksplit = ks; d.nbatch = d.nent = q.B; d.block = 256;
+        d.grid_x = pl.post_norm ? (unsigned)(q.B * q.M) : (unsigned)(((long long)q.M * q.N / 4 + 255) / 256);
+        d.grid_y = pl.post_norm ? 1u : (unsigned)q.B;
+    }
+}
+
+// The one launch body of the tile kernels.
+template <class Cfg, int SCHED>
+int launch_cfg(const GemmParams& p, const TileLaunch& l, bool chunked, hipStream_t st) {
+    auto kern = TileKernel<Cfg, SCHED>::get();
+    if constexpr (Cfg::LDS_BYTES > 0) {
+        static std::atomic<uint64_t> lds_done{0};
+        if (!ensure_dyn_lds((const void*)kern, Cfg::LDS_BYTES, lds_done)) return BD_E_LAUNCH;
+    }
+    // Experiment kept behind bd_set_launch_chunking(1): issue a multi-round problem as several launches of at most one tile per CU
+    // (an mc x nc block of tiles each, via GemmParams::tile_m0 / tile_n0).  Hypothesis: rounds inside one launch drift apart and that
+    // is why 8192x4096x4096 runs 10 % below back-to-back 2048-row launches.  Measured (profiles/r01_launch_chunking.txt): no gain
+    // (-0..3 %, -15 % with 6 tenants) -- the back-to-back figure was warm-cache re-reads of the same operands, not synchronisation.
+    const long long cus = chunked ? num_cus() : 0, B = l.grid_y;
+    if (chunked && (long long)p.tiles_m * p.tiles_n * B > cus && B <= cus) {
+        const long long per = cus / B;                                     // tiles per launch and batch entry
+        // orientation A: all tile rows x as many tile columns as fit; B: all tile columns x as many rows as fit
+        long long mcA = p.tiles_m < per ? p.tiles_m : per, ncA = per / mcA; if (ncA > p.tiles_n) ncA = p.tiles_n;
+        long long ncB = p.tiles_n < per ? p.tiles_n : per, mcB = per / ncB; if (mcB > p.tiles_m) mcB = p.tiles_m;
+        const long long nA = ((p.tiles_m + mcA - 1) / mcA) * ((p.tiles_n + ncA - 1) / ncA);
+        const long long nB = ((p.tiles_m + mcB - 1) / mcB) * ((p.tiles_n + ncB - 1) / ncB);
+        const int mc = (int)(nA <= nB ? mcA : mcB), nc = (int)(nA <= nB ? ncA : ncB);
+        for (int m0 = 0; m0 < p.tiles_m; m0 += mc)
+            for (int n0 = 0; n0 < p.tiles_n; n0 += nc) {
+                GemmParams c = p;
+                c.tile_m0 = m0; c.tile_n0 = n0;
+                c.tiles_m = p.tiles_m - m0 < mc ? p.tiles_m - m0 : mc;
+                c.tiles_n = p.tiles_n - n0 < nc ? p.tiles_n - n0 : nc;
+                if (c.group_m > c.tiles_m) c.group_m = c.tiles_m;
+                hipLaunchKernelGGL(kern, dim3((unsigned)(c.tiles_m * c.tiles_n), l.grid_y), dim3(l.block), l.lds, st, c);
+            }
+        return BD_OK;
+    }
+    hipLaunchKernelGGL(kern, dim3(l.grid_x, l.grid_y, SCHED == S_GEN ? (unsigned)l.nbatch : 1u), dim3(l.block), l.lds, st, p);
+    return BD_OK;
+}
+
+// the reduce launch of a split plan: partial slabs [B][KS][M][N] -> C, with the post-norm where the plan says so
+template <int DT>
+void launch_splitk_reduce(const Problem& q, const TilePlan& pl, const float* part) {
+    const TileLaunch& d = pl.reduce;
+    if (pl.post_norm)
+        hipLaunchKernelGGL((splitk_reduce_norm_kernel<DT>), dim3(d.grid_x), dim3(d.block), 0, q.st, part, (unsigned short*)q.C,
+                           (const unsigned short*)q.pn_w, (unsigned short*)q.pn_h, pl.ks, q.M, q.N, (long long)q.sCb, (long long)q.sCm,
+                           (long long)q.sHb, (long long)q.sHm, (long long)q.s_pnw, q.accumulate, q.pn_eps);
+    else
+        hipLaunchKernelGGL((splitk_reduce_kernel<DT>), dim3(d.grid_x, d.grid_y), dim3(d.block), 0, q.st, part, q.C, q.B, pl.ks, q.M, q.N,
+                           (long long)q.sCb, (int)q.sCm, q.out_dtype == BD_F32 ? 1 : 0, q.accumulate);
+}
+
+// Issues a plan whose tile launches are (FUSED, F32) ones: main and tail through launch_cfg, and behind a split row's launch its reduce launch.
+template <int DT, bool FUSED, bool F32>
+int launch_tile_plan(const Problem& q, const TilePlan& pl) {
+    for (const TileLaunch* l : {&pl.main, &pl.tail}) {
+        if (!l->on) continue;
+        GemmParams p;
+        p.A = (const char*)q.A; p.P = q.P; p.C = (char*)q.C; p.W = (const char*)q.W; p.alpha = q.alpha;
+        p.M = q.M; p.N = q.N; p.K = q.K;
+        p.tiles_m = l->tiles_m; p.tiles_n = l->tiles_n; p.tile_m0 = 0; p.tile_n0 = l->tile_n0; p.ksplit = l->ksplit;
+        p.sAb = q.sAb; p.sPb = q.sPb; p.sCb = q.sCb;
+        p.sAm = (int)q.sAm; p.sCm = (int)q.sCm; p.ldw = (int)q.ldw;
+        p.sAlb = (int)q.sAlb; p.gsz = q.N / q.G;
+        p.round_mode = q.round_mode; p.accumulate = q.accumulate;
+        p.nbatch = l->nbatch; p.nent = l->nent; p.group_m = l->group_m;
+        const int rc = lift_row<DT, FUSED, F32>(l->row, [&](auto tag, auto i) {
+            using Cfg = typename decltype(tag)::type;
+            constexpr TileRow r = TILE_ROWS[decltype(i)::value];
+            if constexpr (r.is(T_SPLIT)) {
+                // fp32 partial slabs [entry * KS + slice][M][N] in the workspace; the residual is added by the reduce launch
+                float* part = (float*)((char*)q.ws + GEMV_TICKET_BYTES);
+                p.C = (char*)part; p.sCm = q.N; p.sCb = (long long)q.M * q.N; p.accumulate = 0;
+                const int rc = launch_cfg<Cfg, r.sched>(p, *l, false, q.st);
+                if (rc == BD_OK) launch_splitk_reduce<DT>(q, pl, part);
+                return rc;
+            } else return launch_cfg<Cfg, r.sched>(p, *l, pl.chunked, q.st);
+        }, TileRowSeq{});
+        if (rc != BD_OK) return rc;
+    }
+    return launch_status();
+}
+
+// the decode families (forced, or the automatic 200)
+template <int DT, bool FUSED>
+int dispatch_decode(const Problem& q, int v) {
     switch (v) {
-        // Shipped MFMA tile kernels: 0 / 5 = delta-only full-tile ping-pong at 256x256 / 256x128 (bd_gemm_pf.h), 8 / 9 / 10 = one-pass
-        // fused (bd_gemm_fx.h), 1 / 2 / 3 = small-M single-barrier tiles (bd_gemm_mfma.h).  The rejected schedules -- 4 (256x256
-        // single barrier), 6 / 7 (half-tile ping-pong), fused 0 / 5 (two k loops over one accumulator set) -- are compiled only with
-        // -DBD_AB_VARIANTS (the native harness); the shipped library answers BD_E_BAD_SHAPE for them.
-        case 0:
-            if constexpr (!FUSED) return launch_tile<GemmCfg<DT, 256, 256, 2, 4, 4, FUSED, OUT_F32, 1>, 2>(q);    // full-tile ping-pong, LUT sign expansion
-#ifdef BD_AB_VARIANTS
-            else return launch_tile<GemmCfg<DT, 256, 256, 2, 4, 4, FUSED, OUT_F32, 2>, 1>(q);   // 2-slot base ring
-#else
-            else return BD_E_BAD_SHAPE;
-#endif
-        case 5:
-            if constexpr (!FUSED) return launch_tile<GemmCfg<DT, 256, 128, 2, 4, 4, FUSED, OUT_F32, 0>, 2>(q);
-#ifdef BD_AB_VARIANTS
-            else return launch_tile<GemmCfg<DT, 256, 128, 2, 4, 4, FUSED, OUT_F32, 0>, 2>(q);
-#else
-            else return BD_E_BAD_SHAPE;
-#endif
-#ifdef BD_AB_VARIANTS
-        case 6: return launch_tile<GemmCfg<DT, 256, 256, 2, 4, 4, FUSED, OUT_F32, 2>, 1>(q);      // half-tile ping-pong (A/B reference)
-        case 7: return launch_tile<GemmCfg<DT, 256, 128, 2, 4, 4, FUSED, OUT_F32, 2>, 1>(q);      // half-tile ping-pong 256x128 (A/B)
-        case 4: return launch_tile<GemmCfg<DT, 256, 256, 2, 4, 4, FUSED, OUT_F32>>(q);   // single-barrier 256x256 (A/B reference)
-#endif
-        case 8:
-            if constexpr (FUSED) return launch_tile<FxCfg<DT, 256, 128, 3, OUT_F32, 1>, 3>(q);
-            else return BD_E_BAD_SHAPE;
-        case 10: {   // one-pass fused, 128x128 tile, split-k over blockIdx.y + reduce launch (forced: KS from the rule, at least 2)
-            if constexpr (FUSED) {
-                int ks = splitk_factor(q.B, q.M, q.N, q.K);
-                if (ks < 2) ks = (q.K / 64 >= 2) ? 2 : 1;
-                if (ks < 2) return BD_E_BAD_SHAPE;
-                return launch_fused_splitk<DT>(q, ks);
-            } else return BD_E_BAD_SHAPE;
-        }
-        case 11:     // one-pass fused, 64x128 tile: up to 64 rows per mask (multi-tenant prefill of short prompts, demo_backend.py:297-299:
-                     // M = 64 x 6 tenants) -- the 128-row tile does twice the MFMA and LDS work for rows that do not exist
-            if constexpr (FUSED) return launch_tile<FxCfg<DT, 64, 128, 4, OUT_F32, 1>, 3>(q);
-            else return BD_E_BAD_SHAPE;
-        case 12:     // one-pass fused, 64x256 tile: wide outputs / many tenants (see the rule above)
-            if constexpr (FUSED) return launch_tile<FxCfg<DT, 64, 256, 3, OUT_F32, 1>, 3>(q);
-            else return BD_E_BAD_SHAPE;
-        case 16:     // pair tiles: two batch entries of <= 64 rows per 128x128 tile (multi-tenant prefill of short prompts)
-            if constexpr (FUSED) { if (!pair_ok(q)) return BD_E_BAD_SHAPE; return launch_pair<DT, OUT_F32>(q); }
-            else return BD_E_BAD_SHAPE;
-        case 17: {   // pair tiles + split-k (narrow outputs: o / down of a 6-tenant request are 96 tiles on 256 CUs)
-            if constexpr (FUSED) {
-                if (!pair_ok(q) || q.N % 8 || q.sCm % 4 || q.sCb % 4) return BD_E_BAD_SHAPE;
-                int ks = pair_splitk(q);
-                if (ks < 2) ks = (q.K / 64 >= 2) ? 2 : 1;
-                if (ks < 2 || ks > q.K / 64) return BD_E_BAD_SHAPE;       // every k slice holds at least one 64-k tile (no empty slices)
-                return launch_pair_splitk<DT>(q, ks);
-            } else return BD_E_BAD_SHAPE;
-        }
-        case 18:     // FOUR-WAVE pair tiles (bd_gemm_w4.h PAIR): one wave per SIMD, wave tile 64 x 64, persistent over (pair, column tile)
-            if constexpr (FUSED) { if (!pair_ok(q)) return BD_E_BAD_SHAPE; return launch_w4_pair<DT, OUT_F32>(q); }
-            else return BD_E_BAD_SHAPE;
-        case 21:     // 18 with the SwiGLU epilogue: the gate|up projection of a multi-tenant request of short prompts (6 x 64 rows), no [M, 2 I] round trip
-            if constexpr (FUSED && !OUT_F32) { if (!pair_ok(q) || q.epilogue != 1) return BD_E_BAD_SHAPE; return launch_w4_pair<DT, false, 1>(q); }
-            else return BD_E_BAD_SHAPE;
-        case 20:     // four-wave fused 128x128 tile, ONE batch entry per tile (prompts of 65 .. 128 rows per tenant; W4Cfg TM = 2, PAIR = 0)
-            if constexpr (FUSED) return launch_w4<W4Cfg<DT, 128, 128, true, OUT_F32, 1 | 8192, 0, 0>>(q);
-            else return BD_E_BAD_SHAPE;
-        case 19: {   // four-wave pair tiles + split-k (the narrow outputs of a multi-tenant request)
-            if constexpr (FUSED) {
-                if (!pair_ok(q) || q.N % 8 || q.sCm % 4 || q.sCb % 4) return BD_E_BAD_SHAPE;
-                int ks = pair_splitk(q);
-                if (ks < 2) ks = 2;
-                while (ks > 1 && (q.K / 64) % ks) --ks;                   // the slices are whole, equal runs of k-tiles
-                if (ks < 2) return BD_E_BAD_SHAPE;
-                return launch_w4_pair_splitk<DT>(q, ks);
-            } else return BD_E_BAD_SHAPE;
-        }
-        case 9:      // one-pass fused, 128x128 tile, 4-slot ring: twice the tiles when 256x128 cannot fill the CUs (128 < M <~ 768)
-            if constexpr (FUSED) return launch_tile<FxCfg<DT, 128, 128, 4, OUT_F32, 1>, 3>(q);
-            else return BD_E_BAD_SHAPE;
-        // (W4Cfg OPT = 1 | 8192: LUT sign expansion + the k loop unrolled by four -- bit-identical outputs, -3.6 / -5.5 % cycles per k-tile,
-        //  +0.6 % on the timed prefill step in a same-box A/B of two library builds; profiles/r05_w4_cycles.txt)
-        case 13:     // four-wave persistent delta-only kernel, 256x256 tile, LUT sign expansion (bd_gemm_w4.h)
-            if constexpr (!FUSED) return launch_w4<W4Cfg<DT, 256, 256, false, OUT_F32, 1 | 8192>>(q);
-            else return BD_E_BAD_SHAPE;
-        case 14:     // four-wave persistent one-pass fused kernel, 256x128 tile, LUT sign expansion (+1.5 % over VALU expansion, same box)
-            if constexpr (FUSED) {
-                if constexpr (!OUT_F32) {
-                    const int cols = (g_forced_variant < 0 && g_tail_split) ? fused_tail_split_cols(q) : -1;
-                    if (cols > 0) {
-                        const int rc = launch_w4<W4Cfg<DT, 256, 128, true, false, 1 | 8192>>(q, cols);
-                        if (rc != BD_OK) return rc;
-                        // the remaining tile columns on 128x128 tiles -- four-wave since round 5 (variant 20's kernel: 5..17 % faster than the
-                        // 8-wave 128x128 tile on every shape measured); same 128-wide tile columns
-                        return launch_w4<W4Cfg<DT, 128, 128, true, false, 1 | 8192, 0, 0>>(q, -1, cols);
-                    }
-                }
-                return launch_w4<W4Cfg<DT, 256, 128, true, OUT_F32, 1 | 8192>>(q);      // (fp32 output: general-form epilogue only)
-            } else return BD_E_BAD_SHAPE;
-        case 15:     // 14 with the SwiGLU epilogue (bd_binary_linear_swiglu: 8-interleaved gate|up pair, C has N/2 columns)
-            if constexpr (FUSED && !OUT_F32) return launch_w4<W4Cfg<DT, 256, 128, true, false, 1 | 8192, 1>>(q);
-            else return BD_E_BAD_SHAPE;
-        case 1: return launch_tile<GemmCfg<DT, 128, 256, 1, 4, 4, FUSED, OUT_F32>>(q);
-        case 2: return launch_tile<GemmCfg<DT, 64, 256, 1, 4, 4, FUSED, OUT_F32>>(q);
-        case 3: return launch_tile<GemmCfg<DT, 32, 256, 1, 4, 4, FUSED, OUT_F32>>(q);
-        case 100: return launch_generic<DT, FUSED, OUT_F32>(q);
         // decode: the VALU sign-flip kernel is as fast or faster on the fused Linear shapes (profiles/r01_decode_kernels.txt);
         // the MFMA + LUT kernel wins when the delta dominates (delta-only with >= 8 masks) and on narrow outputs (k/v projections)
         // ... and whenever a mask is shared by >= 2 rows (M > 1 or a broadcast mask): it expands each word once for all rows
@@ -1362,7 +1332,24 @@ int dispatch3(const Problem& q) {
     }
 }
 
+// Issues a plan.  The order in which this function names its callees is the order in which the compiler is asked for their kernels, and so the
+// kernels' order in the code object: per dtype the fused fp32 tile launches, the fused decode families, the fused 16-bit tile launches, the
+// delta-only fp32 ones, the delta-only decode families, the delta-only 16-bit ones -- where they lay before the dispatch was split into a plan
+// and a launcher.  Byte-identical kernels at other addresses measured +0.2 % on the prefill step (profiles/prefill_dispatch_refactor.txt).
+template <int DT>
+int launch_plan(const Problem& q, const TilePlan& pl, bool fused) {
+    const bool tile = pl.variant < 200, f32 = pl.main.f32 != 0;      // (a tail launch writes what the main launch writes)
+    if (tile && fused && f32) return launch_tile_plan<DT, true, true>(q, pl);
+    if (fused && !tile) return dispatch_decode<DT, true>(q, pl.variant);
+    if (fused) return launch_tile_plan<DT, true, false>(q, pl);
+    if (tile && f32) return launch_tile_plan<DT, false, true>(q, pl);
+    if (!tile) return dispatch_decode<DT, false>(q, pl.variant);
+    return launch_tile_plan<DT, false, false>(q, pl);
+}
+
 int dispatch(const Problem& q) {
+    TilePlan& pl = t_tile_plan;
+    pl = TilePlan{};
     if (q.B < 0 || q.M < 0 || q.N < 0 || q.K < 0) return BD_E_BAD_SHAPE;
     if (q.K % 32) return BD_E_K_NOT_MULTIPLE;
     if (q.dtype != BD_F16 && q.dtype != BD_BF16) return BD_E_BAD_DTYPE;
@@ -1372,16 +1359,28 @@ int dispatch(const Problem& q) {
     if (q.B > 65535) return BD_E_BAD_SHAPE;
     if (!q.A || !q.P || !q.C) return BD_E_NULL;
     if ((q.W || q.accumulate) && !q.alpha) return BD_E_NULL;
-    const bool fused = q.W != nullptr, f32 = q.out_dtype == BD_F32;
     if (q.K == 0) return BD_E_BAD_SHAPE;
-#define BD_D(DT) (fused ? (f32 ? dispatch3<DT, true, true>(q) : dispatch3<DT, true, false>(q)) \
-                        : (f32 ? dispatch3<DT, false, true>(q) : dispatch3<DT, false, false>(q)))
-    return q.dtype == BD_BF16 ? BD_D(DT_BF16) : BD_D(DT_F16);
-#undef BD_D
+    const bool fused = q.W != nullptr;
+    tile_plan(q, fused, q.out_dtype == BD_F32, num_cus(), pl);
+    if (pl.variant >= 0) t_last_variant = pl.variant;
+    if (pl.rc != BD_OK || g_gemm_dry_run) return pl.rc;
+    return q.dtype == BD_BF16 ? launch_plan<DT_BF16>(q, pl, fused) : launch_plan<DT_F16>(q, pl, fused);
 }
 
 }  // namespace
 
+extern "C" int bd_set_gemm_dry_run(int on) { g_gemm_dry_run = on ? 1 : 0; return BD_OK; }
+extern "C" int bd_last_gemm_plan(int32_t* out, int n) {
+    const TilePlan& pl = t_tile_plan;
+    int32_t rec[BD_GEMM_PLAN_INTS] = {pl.rc, pl.variant, pl.ks, pl.tail_col, (int32_t)(pl.ws_bytes & 0xffffffffll), (int32_t)(pl.ws_bytes >> 32), pl.post_norm};
+    int at = 7;
+    for (const TileLaunch* l : {&pl.main, &pl.tail, &pl.reduce})
+        for (int v : {l->on ? l->bm : -1, l->bn, l->sched, l->tiles_m, l->tiles_n, l->tile_n0, l->group_m, l->ksplit, l->nbatch, l->nent, (int)l->grid_x,
+                      (int)l->grid_y, l->block, l->lds})
+            rec[at++] = v;
+    for (int i = 0; out && i < n && i < BD_GEMM_PLAN_INTS; ++i) out[i] = rec[i];
+    return BD_GEMM_PLAN_INTS;
+}
 extern "C" int bd_last_decode_form(void) { return t_last_plan.form; }
 extern "C" int bd_set_decode_dry_run(int on) { g_decode_dry_run = on ? 1 : 0; return BD_OK; }
 extern "C" int bd_last_decode_plan(int32_t* out, int n) {
@@ -1399,10 +1398,10 @@ extern "C" int64_t bd_gemm_workspace_bytes(int B, int M, int N, int K) {
         // mid-size M: split-k partial slabs of the fused tile kernel -- only where the automatic rule really splits (or a test
         // forces the split-k variant); every other tile-kernel launch needs no scratch at all
         if (M > 16 && M <= 512 && K % 64 == 0 && N % 8 == 0) {
-            int ks = splitk_factor(B, M, N, K);
+            int ks = splitk_factor(B, M, N, K, num_cus());
             if (ks < 2 && g_forced_variant == 10) ks = 2;
             if (B >= 2 && M <= 64) {                      // pair tiles (variants 16 / 17) split by their own rule
-                int kp = pair_splitk_dims(B, N, K);
+                int kp = pair_splitk_dims(B, N, K, num_cus());
                 if (kp < 2 && (g_forced_variant == 17 || g_forced_variant == 19)) kp = 2;
                 if (kp > ks) ks = kp;
             }
@@ -1436,7 +1435,7 @@ extern "C" int bd_delta_bmm(const void* A, const int32_t* P, void* C, int B, int
     if (alpha && !accumulate) {
         // C = alpha * acc without a C_in: express as the fused epilogue of an all-zero base is not worth a kernel;
         // zero C then accumulate (two tiny ops on the output only).
-        if (B > 0 && M > 0 && N > 0 && C) {
+        if (B > 0 && M > 0 && N > 0 && C && !g_gemm_dry_run) {
             const size_t esz = out_dtype == BD_F32 ? 4 : 2;
             if (sCm == N && (sCb == (int64_t)M * N || B == 1)) {
                 if (hipMemsetAsync(C, 0, (size_t)B * M * N * esz, q.st) != hipSuccess) return BD_E_LAUNCH;
@@ -1654,12 +1653,11 @@ extern "C" int bd_binary_linear_residual_norm(const void* X, const void* W, cons
     if (M <= GEMV_MAX_M || N % 8 || N > 8192 || sYm % 8 || sYb % 8 || sHm % 8 || sHb % 8 || s_nw % 8 || s_nw < 0 || !aligned16(Y) || !aligned16(H) ||
         !aligned16(norm_w) || sYb != (int64_t)M * sYm || sHb != (int64_t)M * sHm)
         return BD_E_BAD_SHAPE;
-    t_post_norm_done = 0;
     Problem e{};
     e.pn_w = norm_w; e.s_pnw = s_nw; e.pn_eps = eps; e.pn_h = H; e.sHb = sHb; e.sHm = sHm;
     const int rc = binary_linear_impl(X, W, P, alpha, Y, B, M, N, K, sXb, sXm, ldw, sPb, sAlb, G, sYb, sYm, dtype, dtype, 1, 0, 0, ws, ws_bytes,
                                       stream, e);
-    if (rc != BD_OK || t_post_norm_done) return rc;
+    if (rc != BD_OK || t_tile_plan.post_norm || g_gemm_dry_run) return rc;
     return bd_srv_rmsnorm(Y, norm_w, H, B * M, N, sYm, sHm, s_nw, M, eps, dtype, stream);
 }
 

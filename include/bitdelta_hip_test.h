@@ -3,7 +3,9 @@
  * Everything here is thread-local state of the calling thread, exists for same-process A/B measurements and for tests that pin a kernel
  * family, and is NOT part of the drop-in boundary: no reference interface corresponds to any of it (the reference's only tunable is
  * Triton's autotune cache, bitdelta/binary_gemm_kernel.py:48-60 / :186-198, replaced here by a static shape -> variant table).  Production
- * callers never include this header. */
+ * callers never include this header.
+ * Two pairs of hooks make the dispatch itself observable without a GPU: bd_set_decode_dry_run / bd_last_decode_plan (the streaming decode
+ * Linear) and bd_set_gemm_dry_run / bd_last_gemm_plan (the prefill-size tile kernels, variants 0 - 21 and 100). */
 #ifndef BITDELTA_HIP_TEST_H
 #define BITDELTA_HIP_TEST_H
 #include "bitdelta_hip.h"
@@ -45,6 +47,26 @@ extern "C" {
 int bd_set_gemm_variant(int variant);
 /* which family the LAST call on this thread dispatched to (same codes as above) */
 int bd_last_gemm_variant(void);
+/* What the library decided about the LAST bd_delta_bmm / bd_binary_linear* call of this thread that reached its dispatcher (tile_plan in
+ * csrc/bd_api.hip): copies up to n of the BD_GEMM_PLAN_INTS values below into out and returns BD_GEMM_PLAN_INTS.
+ *   [0] the call's return code as far as the plan decides it (a refusal: the fields decided until then)
+ *   [1] bd_last_gemm_variant() of the call (>= 200: a decode family, nothing further is filled)   [2] k slices (1 = unsplit)
+ *   [3] variant 14's tail split: first 128-wide tile column of the tail launch (-1 = none)   [4] [5] workspace bytes the plan needs, low / high word
+ *   [6] 1 = the reduce launch carries the RMSNorm of bd_binary_linear_residual_norm
+ *   [7..20] main launch, [21..34] tail launch, [35..48] reduce launch, each: the tile's rows BM and columns BN (BM = -1: not issued; reduce: 0 0),
+ *   schedule (0 single barrier, 1 half-tile ping-pong, 2 full-tile ping-pong, 3 one-pass fused, 4 four-wave persistent, 5 generic; reduce: 1 = with
+ *   the norm), then GemmParams tiles_m, tiles_n, tile_n0, group_m, ksplit, nbatch, nent, then grid x, grid y (generic kernel: z = nbatch),
+ *   threads per block, dynamic LDS bytes */
+#define BD_GEMM_PLAN_INTS 49
+int bd_last_gemm_plan(int32_t* out, int n);
+/* 1 = the calls of this thread that reach the GEMM dispatcher are DRY RUNS: planned, recorded (bd_last_gemm_plan, bd_last_gemm_variant) and
+ * answered with the code the launch would return, without a launch, a memory operation or a change of any device state -- no pointer is
+ * dereferenced, bd_delta_bmm's zero-fill and bd_binary_linear_residual_norm's norm launch included.  What a dry run still does is ASK: the CU
+ * count comes from hipGetDevice / hipDeviceGetAttribute (read-only; 256 without a device), as in the decode dry run.  One exception to the return
+ * code: a plan that ends in a decode family records the variant 200 - 800 it was handed to and answers BD_OK there, so what the decode launchers
+ * themselves would refuse (a forced 800 on a fused call, a forced id no family owns such as 265, a forced 600 outside the streaming envelope) is
+ * not seen by a dry run. */
+int bd_set_gemm_dry_run(int on);
 /* tuning hook: tile walk order of the MFMA tile kernels -- groups of `group_m` tile rows, m fastest inside a group, then n
  * (1 = n fastest, >= tiles_m = m fastest, 0 = automatic).  Results do not depend on it. */
 int bd_set_tile_group_m(int group_m);

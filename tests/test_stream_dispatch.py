@@ -45,6 +45,14 @@ def test_compiled_stream_kernels_are_the_golden_list(tmp_path):
     assert len(want) == 592 and want == sorted(set(want))
     assert got == want, (f"compiled but not listed: {sorted(set(got) - set(want))[:5]}, listed but not compiled: {sorted(set(want) - set(got))[:5]} "
                          "(tests/golden/stream_kernel_forms.txt is edited on purpose, with the dispatch)")
+    # ... and the prefill-size tile kernels (TILE_ROWS and its lifter), the generic kernel and the split-k reduce launches: tile_kernel_forms.txt
+    tile = ("delta_gemm_kernel<", "delta_gemm_pf_kernel<", "delta_gemm_fx_kernel<", "delta_gemm_w4_kernel<", "delta_gemm_generic_kernel<",
+            "splitk_reduce_kernel<", "splitk_reduce_norm_kernel<")
+    got = sorted({s.split("__device_stub__", 1)[1] for s in syms if "__device_stub__" in s and s.split("__device_stub__", 1)[1].startswith(tile)})
+    want = golden_lines("tile_kernel_forms.txt")
+    assert len(want) == 84 and want == sorted(set(want))
+    assert got == want, (f"compiled but not listed: {sorted(set(got) - set(want))[:5]}, listed but not compiled: {sorted(set(want) - set(got))[:5]} "
+                         "(tests/golden/tile_kernel_forms.txt is edited on purpose, with the dispatch)")
 
 
 def test_sweep_reaches_every_form_and_refuses_enough():
