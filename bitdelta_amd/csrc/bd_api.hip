@@ -23,6 +23,7 @@
 #endif
 #include "bd_serving.h"
 #include "bd_attn_prefill.h"
+#include "bd_token_nll.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2135,5 +2136,28 @@ extern "C" int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, co
     if (!ensure_dyn_lds(fn, PREFILL_ATTN_LDS, lds_done[di])) return BD_E_LAUNCH;
     if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
     else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    return launch_status();
+}
+
+// (behind every kernel that existed before it: see the note above bd_srv_prefill_attention_cached)
+extern "C" int bd_srv_token_nll(const void* logits, int64_t sl, int V, const int64_t* labels, float* nll, float* lse, int R, int dtype,
+                                void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (!logits || !labels || !nll) return BD_E_NULL;
+    if (sl % 8 || sl < V || !aligned16(logits) || !aligned_to(labels, 8) || !aligned_to(nll, 4) || !aligned_to(lse, 4)) return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    // the form depends on V alone: <= 8192 / <= 32768 hold the row in 4 / 16 sixteen-byte registers per thread, longer rows are read twice
+#define BD_NLL_LAUNCH(DT, NV)                                                                                                           \
+    hipLaunchKernelGGL((token_nll_kernel<DT, NV>), dim3((unsigned)R), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V, \
+                       (const long long*)labels, nll, lse)
+    const int nv = V <= 2048 * 4 ? 4 : V <= 2048 * NLL_NV_MAX ? NLL_NV_MAX : 0;
+    if (dtype == BD_BF16) {
+        if (nv == 4) BD_NLL_LAUNCH(DT_BF16, 4); else if (nv == NLL_NV_MAX) BD_NLL_LAUNCH(DT_BF16, NLL_NV_MAX); else BD_NLL_LAUNCH(DT_BF16, 0);
+    } else {
+        if (nv == 4) BD_NLL_LAUNCH(DT_F16, 4); else if (nv == NLL_NV_MAX) BD_NLL_LAUNCH(DT_F16, NLL_NV_MAX); else BD_NLL_LAUNCH(DT_F16, 0);
+    }
+#undef BD_NLL_LAUNCH
     return launch_status();
 }

@@ -777,6 +777,12 @@ class TenantDecoder(nn.Module):
         """ids [T, S]; pos_idx [S] (device, positions of these tokens in the cache); attn_mask [T, 1, S, L] bool.
         Returns the logits of the LAST position, [T, vocab].  x: the embedded tokens when the caller already has them (step_begin).
         ragged=(pos [T], active [T]): one decode token per tenant, each at its own position (TenantSession); pos_idx and attn_mask are unused."""
+        x = self._hidden(ids, pos_idx, cache, attn_mask, x=x, ragged=ragged)
+        last = self._norm(x[:, -1:, :], self.final_norm)
+        return tenant_linear(last, self.lm_head)[:, 0, :]                     # per-tenant lm_head: one launch
+
+    def _hidden(self, ids, pos_idx, cache, attn_mask, x=None, ragged=None):
+        """forward's layers: the residual stream after the last layer, [T, S, hidden], before the final norm (every row: score reads them)"""
         T, S = ids.shape
         _, _, _, heads, kvh, _ = self.cfg
         assert ragged is None or S == 1
@@ -793,8 +799,7 @@ class TenantDecoder(nn.Module):
         for li, layer in enumerate(self.layers):
             nxt = self.layers[li + 1] if li + 1 < len(self.layers) else None
             x, ssq_valid, h_in = self._layer(layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid, nxt, h_in, ragged=ragged)
-        last = self._norm(x[:, -1:, :], self.final_norm)
-        return tenant_linear(last, self.lm_head)[:, 0, :]                     # per-tenant lm_head: one launch
+        return x
 
     # ---------------------------------------------------------------- request handling (demo_backend.py:261-315 + :190-258)
     def prepare(self, prompts):
@@ -812,7 +817,8 @@ class TenantDecoder(nn.Module):
         return ids.to(self.dev), am.to(self.dev)
 
     @torch.no_grad()
-    def prefill(self, ids, attention_mask, cache):
+    def prefill(self, ids, attention_mask, cache, hidden=False):
+        """hidden=True: every row of the residual stream after the last layer ([T, L, hidden], _hidden) instead of the last row's logits"""
         T, L = ids.shape
         pos_idx = torch.arange(L, device=self.dev)
         cache["valid"].zero_()
@@ -828,9 +834,87 @@ class TenantDecoder(nn.Module):
         left_padded = bool((am[:, 1:] | ~am[:, :-1]).all()) if L > 1 else True
         cache["kv_start"] = (L - am.sum(dim=1)).to(torch.int32) if (left_padded and self.hip_prefill_attention) else None
         try:
-            return self.forward(ids, pos_idx, cache, mask)
+            return (self._hidden if hidden else self.forward)(ids, pos_idx, cache, mask)
         finally:
             cache["kv_start"] = None
+
+    # ---------------------------------------------------------------- scoring (eval_ppl.py:61-83, for T fine-tunes in one pass over the base)
+    def _score_args(self, seqs, targets_from):
+        """score's argument checks, all on the host and before any launch: (token lists, first scored index per tenant, padded length)"""
+        if torch.is_tensor(seqs):
+            if seqs.dim() != 2 or seqs.dtype != torch.long:
+                raise ValueError("a tensor of sequences is a [T, n] LongTensor")
+            seqs = seqs.tolist()
+        seqs = [[int(v) for v in s] for s in seqs]
+        if len(seqs) != self.T:
+            raise ValueError("one sequence per tenant: got %d for %d tenants" % (len(seqs), self.T))
+        vocab = self.cfg[5]
+        for s in seqs:
+            if len(s) < 2:
+                raise ValueError("a sequence needs at least 2 tokens to score one")
+            if min(s) < 0 or max(s) >= vocab:
+                raise ValueError("token id outside the vocabulary of %d" % vocab)
+        if isinstance(targets_from, (list, tuple)):
+            if len(targets_from) != self.T:
+                raise ValueError("targets_from: one int, or one per tenant")
+            first = [operator.index(v) for v in targets_from]
+        else:
+            first = [operator.index(targets_from)] * self.T
+        if min(first) < 0:
+            raise ValueError("targets_from is an index into the sequence: >= 0")
+        L = -(-max(len(s) for s in seqs) // MIN_PAD) * MIN_PAD
+        if L > self.max_len:
+            raise ValueError("the sequences pad to %d tokens, beyond this decoder's max_len of %d" % (L, self.max_len))
+        return seqs, [max(1, f) for f in first], L
+
+    @torch.no_grad()
+    def score(self, seqs, targets_from=0, row_chunk=512, hip_nll=True):
+        """Teacher-forced token losses of T sequences, one per tenant (lengths >= 2, may differ; or a [T, n] LongTensor): a list of T float32
+        device tensors, entry i of tensor t = -log p_t(seq_t[i] | seq_t[:i]) for i >= max(1, targets_from[t]) and exactly 0 before it.
+        targets_from: an int, or one per tenant.  The sequences are left-padded with token 0 to a common multiple of 64 (prepare()'s power of two
+        and MAX_PROMPT are the demo's request rules, not scoring's) and run through the batched prefill on a scratch KV cache of that length: the
+        decoder's own cache, its captured graphs and live sessions are not touched.  Only the rows that predict a scored token go through the
+        final norm and the lm_head, row_chunk rows per tenant at a time (torch.bmm: an M > 16 per-tenant Linear is the BLAS's), each chunk
+        through serving_ops.token_nll -- the [T, L, vocab] logits never exist.  hip_nll=False: the stock tail, log_softmax(chunk.float()) + gather."""
+        seqs, first, L = self._score_args(seqs, targets_from)
+        row_chunk = operator.index(row_chunk)
+        if row_chunk < 1:
+            raise ValueError("row_chunk >= 1")
+        T = self.T
+        ids = torch.zeros(T, L, dtype=torch.long)
+        am = torch.zeros(T, L, dtype=torch.bool)
+        counts = [max(len(s) - f, 0) for s, f in zip(seqs, first)]           # scored tokens per tenant
+        M = max(max(counts), 1)
+        # row j of tenant t predicts the token at padded column rows[t, j] + 1.  Tenants with fewer scored tokens are filled with the last row and
+        # the ignore label: those entries land in a spare column L of the result and are exactly 0
+        rows = torch.full((T, M), L - 1, dtype=torch.long)
+        labels = torch.full((T, M), -100, dtype=torch.long)
+        for t, (s, f, c) in enumerate(zip(seqs, first, counts)):
+            pad = L - len(s)
+            ids[t, pad:] = torch.tensor(s, dtype=torch.long)
+            am[t, pad:] = True
+            if c:
+                rows[t, :c] = torch.arange(pad + f - 1, L - 1)
+                labels[t, :c] = ids[t, pad + f:]
+        ids, am, rows, labels = ids.to(self.dev), am.to(self.dev), rows.to(self.dev), labels.to(self.dev)
+        x = self.prefill(ids, am, self.new_cache(L), hidden=True)
+        t_idx = torch.arange(T, device=self.dev).view(T, 1)
+        h = self._norm(x[t_idx, rows], self.final_norm)                      # [T, M, hidden]: the predicting rows only
+        head_t = self.lm_head.transpose(1, 2)
+        vocab = self.lm_head.shape[1]
+        out = torch.zeros(T, L + 1, dtype=torch.float32, device=self.dev)
+        for c0 in range(0, M, row_chunk):
+            c1 = min(c0 + row_chunk, M)
+            logits = torch.bmm(h[:, c0:c1], head_t)                          # [T, c, vocab]
+            lab = labels[:, c0:c1].reshape(-1)
+            if hip_nll:
+                nll = ops.token_nll(logits.view(-1, vocab), lab)
+            else:
+                lp = F.log_softmax(logits.view(-1, vocab).float(), dim=-1)
+                keep = lab >= 0
+                nll = torch.where(keep, -lp.gather(1, lab.clamp(min=0)[:, None])[:, 0], torch.zeros((), device=self.dev))
+            out[t_idx, rows[:, c0:c1] + 1] = nll.view(T, c1 - c0)
+        return [out[t, L - len(s):L] for t, s in enumerate(seqs)]
 
     @torch.no_grad()
     def prefill_chunk(self, ids, q0, cache, kv_start=None):

@@ -294,6 +294,31 @@ def sample_rows(logits, temperature, top_k, top_p, seed, draw, dbg=None):
     return tok
 
 
+def token_nll(logits, labels, lse=False):
+    """nll[r] = -log softmax(logits[r])[labels[r]] for logits [R, V] (16-bit) and labels int64 [R]; include/bitdelta_hip.h (bd_srv_token_nll) is
+    the definition.  A label outside [0, V) is ignored: exactly 0.  Returns nll, float32 [R] -- or (nll, lse) with lse=True, lse the rows'
+    log-sum-exp.  Rows whose layout the entry point does not take (last dimension strided, a row stride that is no multiple of 8 -- a [R, 32001]
+    tensor --, a misaligned start) are copied into rows of V rounded up to 8 elements; the padding is never read into a result."""
+    require_gpu(logits, labels)
+    assert logits.dim() == 2 and labels.dtype == torch.long and labels.numel() == logits.shape[0]
+    R, V = logits.shape
+    V8 = (V + 7) // 8 * 8                                   # the kernel reads whole 16-byte vectors: a row occupies V8 elements
+    sl = logits.stride(0) if R > 1 else V8
+    last = logits.storage_offset() + (R - 1) * sl + V8      # ... and the last row's must lie inside the tensor's storage
+    if (logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16
+            or last * logits.element_size() > logits.untyped_storage().nbytes()):
+        padded = torch.empty((R, V8), device=logits.device, dtype=logits.dtype)
+        padded[:, :V].copy_(logits)
+        logits, sl = padded, V8
+    labels = labels.contiguous()
+    nll = torch.empty(R, dtype=torch.float32, device=logits.device)
+    row_lse = torch.empty(R, dtype=torch.float32, device=logits.device) if lse else None
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_token_nll(ptr(logits), sl, V, ptr(labels), ptr(nll), ptr(row_lse), R, DTYPE_CODE[logits.dtype], stream_ptr()),
+              "srv_token_nll")
+    return (nll, row_lse) if lse else nll
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

@@ -323,6 +323,28 @@ int bd_srv_step_end_sample(const void* logits, int64_t sl, int V, int64_t* tok, 
                            const int64_t* stop_ids, int ns, int64_t* pos, int64_t* n, const int64_t* limit, void* active, void* done, int Lc,
                            const float* temperature, const int32_t* top_k, const float* top_p, const int64_t* seed, int32_t* dbg, int T,
                            int dtype, void* stream);
+/* bd_srv_token_nll: the tail of scoring (the reference's eval_ppl.py): each row of 16-bit logits and its label become the token's negative
+ * log-likelihood, nll[r] = -log softmax(logits[r, :V])[labels[r]], and optionally the row's log-sum-exp.  The definition, with l the row's V
+ * values, m = max_i l_i and S = sum_i exp(l_i - m):
+ *     lse[r] = m + ln S            nll[r] = ln S - (l_label - m)
+ *   Labels: a label outside [0, V) is IGNORED (-100 is the reference's ignore value): nll[r] is then exactly 0.0f; lse[r] is written all the same.
+ *   Non-finite rows: a row that holds a NaN or a +inf, or nothing finite, gives lse = NaN and nll = NaN (torch.log_softmax's answer) unless the
+ *     label is ignored.  -inf logits next to finite ones have weight 0; a label that sits on one gives nll = +inf, and lse stays finite.
+ *   A value is a PURE FUNCTION of its row and label: it does not depend on R, on the row's index, on sl, on the other rows, or on graph or eager
+ *     execution.  The masses exp(l_i - m) are fp32 (hardware exp2), added eight at a time (one aligned 16-byte vector, pairwise, inside one
+ *     thread) and from there on in 2^-40 fixed point: every cross-thread sum is an integer sum.  No floating-point atomics.  ln S and the two
+ *     final sums are fp64, rounded once to fp32.
+ *   Accuracy: |nll - exact| <= 2^-19 (1 + |exact|), and the same for lse.  The two terms of nll are both >= 0, so nothing cancels; l - m is exact
+ *     in fp32 for fp16 and correct to an fp32 ulp for bf16; a mass carries <= 2^-24 (|l_i - m| + 3) relative error and, weighted by the softmax,
+ *     sum_i p_i (m - l_i) <= ln V, so ln S is off by at most 2^-24 (ln V + 6) + V 2^-43 (1.0e-6 at V = 32000); the result's rounding adds 2^-24
+ *     relative.  tests/nll_ref.py restates the definition in fp64.
+ * logits [R, V] fp16 / bf16 with row stride sl (elements); labels int64 [R]; nll fp32 [R]; lse fp32 [R] or NULL.  Any 1 <= V <= 2^22 (a resized
+ * vocabulary such as 32001 included: the tail that is not a multiple of 8 is masked inside the kernel); elements V .. sl - 1 of a row may hold
+ * anything and never reach a result.  Checked before any device call: R == 0 -> BD_OK, nothing launched; R < 0, V < 1, V > 2^22 (the integer
+ * sum's headroom), sl < V, sl % 8 != 0, logits not 16-byte aligned, nll / lse not 4-byte or labels not 8-byte aligned -> BD_E_BAD_SHAPE; logits,
+ * labels or nll NULL -> BD_E_NULL; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE.  One 256-thread block per row; up to V = 32768 the row is read from
+ * global memory exactly once and held in registers, a longer row twice. */
+int bd_srv_token_nll(const void* logits, int64_t sl, int V, const int64_t* labels, float* nll, float* lse, int R, int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
