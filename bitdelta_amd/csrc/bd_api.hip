@@ -24,6 +24,7 @@
 #include "bd_serving.h"
 #include "bd_attn_prefill.h"
 #include "bd_token_nll.h"
+#include "bd_logprobs.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2160,4 +2161,41 @@ extern "C" int bd_srv_token_nll(const void* logits, int64_t sl, int V, const int
     }
 #undef BD_NLL_LAUNCH
     return launch_status();
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// One body for the two entry points: n == NULL is bd_srv_token_logprobs (R rows), otherwise bd_srv_step_logprobs (T tenants, cap entries each).
+static int token_logprobs_launch(const void* logits, int64_t sl, int V, const int64_t* tok, const int64_t* n, int64_t* lp_n, float* lp,
+                                 int32_t* top_id, float* top_lp, int cap, int top_n, int R, int dtype, bool step, void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX || cap < 0) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (top_n < 0 || top_n > LP_TOP_MAX || top_n > V) return BD_E_BAD_SHAPE;
+    if (!logits || !tok || !lp || (step && (!n || !lp_n)) || (top_n > 0 && (!top_id || !top_lp))) return BD_E_NULL;
+    if (V % 8 || sl % 8 || sl < V || !aligned16(logits) || !aligned_to(tok, 8) || !aligned_to(n, 8) || !aligned_to(lp_n, 8) || !aligned_to(lp, 4) ||
+        !aligned_to(top_id, 4) || !aligned_to(top_lp, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    // the form depends on V alone, as in bd_srv_token_nll: <= 8192 / <= 32768 hold the row in 4 / 16 sixteen-byte registers per thread
+#define BD_LP_LAUNCH(DT, NV)                                                                                                                 \
+    hipLaunchKernelGGL((token_logprobs_kernel<DT, NV>), dim3((unsigned)R), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V, \
+                       (const long long*)tok, (const long long*)n, (long long*)lp_n, lp, (int*)top_id, top_lp, cap, top_n)
+    const int nv = V <= 2048 * 4 ? 4 : V <= 2048 * NLL_NV_MAX ? NLL_NV_MAX : 0;
+    if (dtype == BD_BF16) {
+        if (nv == 4) BD_LP_LAUNCH(DT_BF16, 4); else if (nv == NLL_NV_MAX) BD_LP_LAUNCH(DT_BF16, NLL_NV_MAX); else BD_LP_LAUNCH(DT_BF16, 0);
+    } else {
+        if (nv == 4) BD_LP_LAUNCH(DT_F16, 4); else if (nv == NLL_NV_MAX) BD_LP_LAUNCH(DT_F16, NLL_NV_MAX); else BD_LP_LAUNCH(DT_F16, 0);
+    }
+#undef BD_LP_LAUNCH
+    return launch_status();
+}
+
+extern "C" int bd_srv_token_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, float* lp, int32_t* top_id, float* top_lp,
+                                     int top_n, int R, int dtype, void* stream) {
+    return token_logprobs_launch(logits, sl, V, tok, nullptr, nullptr, lp, top_id, top_lp, 0, top_n, R, dtype, false, stream);
+}
+
+extern "C" int bd_srv_step_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, const int64_t* n, int64_t* lp_n, float* lp,
+                                    int32_t* top_id, float* top_lp, int cap, int top_n, int T, int dtype, void* stream) {
+    return token_logprobs_launch(logits, sl, V, tok, n, lp_n, lp, top_id, top_lp, cap, top_n, T, dtype, true, stream);
 }

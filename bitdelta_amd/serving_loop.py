@@ -1054,10 +1054,12 @@ class TenantDecoder(nn.Module):
         """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
-    def session(self, max_stop_ids=8, sampling=False):
+    def session(self, max_stop_ids=8, sampling=False, logprobs=None):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
-        request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them."""
-        return TenantSession(self, max_stop_ids, sampling=sampling)
+        request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
+        logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
+        (TenantSession.result_logprobs); None, the default, keeps nothing and adds no launch."""
+        return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1137,6 +1139,33 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 GREEDY = sampling_params()
 
 
+def logprobs_count(logprobs):
+    """The logprobs= argument of a session, validated on the host: None (nothing is kept) or an integer 0 <= k <= 20 (0: the chosen token's
+    log-probability only; k: the k most probable alternatives with it).  A bool, a non-integer or a value outside the range raises ValueError."""
+    if logprobs is None:
+        return None
+    try:
+        if isinstance(logprobs, bool):
+            raise TypeError
+        k = operator.index(logprobs)
+    except TypeError:
+        raise ValueError("logprobs = %r: None or an integer is required" % (logprobs,))
+    if not (0 <= k <= ops.LOGPROBS_MAX):
+        raise ValueError("logprobs = %r: 0 <= logprobs <= %d is required" % (logprobs, ops.LOGPROBS_MAX))
+    return k
+
+
+def logprobs_slot(n, lp_n, cap):
+    """serving_ops.step_logprobs' rule for one tenant on host integers: its token count n against the launch's own counter lp_n and the cap entries
+    of its buffers.  Returns (j, lp_n'): the entry written (None: nothing) and the counter afterwards.  A tenant whose count did not move is not
+    touched; otherwise the entry is that of the token just stored at out[t, n - 1], kept when it lies inside the buffers, and the counter follows
+    n -- so the entries 0 .. min(n, cap) - 1 that result_logprobs reports are exactly the ones written, entry j with token j."""
+    if n == lp_n:
+        return None, lp_n
+    j = n - 1
+    return (j if 0 <= j < cap else None), n
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -1151,11 +1180,19 @@ class TenantSession:
     conversation and no turn reuses the draws of the turn before; a caller who wants fresh randomness passes a new seed.  Without sampling=True the
     session is greedy and refuses non-default sampling arguments (ValueError).
 
+    logprobs=k (0 .. 20; logprobs_count): the session keeps, per emitted token, its log-probability and the k most probable tokens of its step
+    with theirs (result_logprobs; include/bitdelta_hip.h, bd_srv_token_logprobs, defines an entry) -- the model's own distribution, softmax of
+    the logits at temperature 1 before top-k / top-p, whatever the request sampled with.  One more launch ends the step
+    (serving_ops.step_logprobs, behind the step-end launch) and writes the entry of every tenant whose token count moved; the first token's
+    entry comes from the prefill's logits on the device.  The count is the session's: it sizes the buffers and the captured graph.  None keeps
+    nothing and launches nothing.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full; 0 = still active or never submitted."""
 
-    def __init__(self, dec, max_stop_ids=8, sampling=False):
+    def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None):
+        self.logprobs = logprobs_count(logprobs)
         _, _, _, heads, kvh, _ = dec.cfg
         if not (dec.fast_glue and dec.step_kernels):
             raise ValueError("a session runs on the HIP glue and step kernels (fast_glue, step_kernels); there is no stock-op ragged step")
@@ -1185,6 +1222,13 @@ class TenantSession:
             self.top_k = torch.zeros(T, dtype=torch.int32, device=dev)
             self.top_p = torch.ones(T, dtype=torch.float32, device=dev)
             self.seed = torch.zeros(T, dtype=torch.long, device=dev)          # the seed's 64 bits
+        if self.logprobs is not None:                 # entry [t, j] belongs to out[t, j]; entries at or past n[t] are unspecified
+            cap, k = self.out.shape[1], self.logprobs
+            self.lp_n = torch.zeros(T, dtype=torch.long, device=dev)          # step_logprobs' own counter: follows n
+            self.lp = torch.zeros(T, cap, dtype=torch.float32, device=dev)
+            self.top_id = torch.zeros(T, cap, k, dtype=torch.int32, device=dev)
+            self.top_lp = torch.zeros(T, cap, k, dtype=torch.float32, device=dev)
+        self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
         dec._sessions.add(self)
@@ -1206,6 +1250,8 @@ class TenantSession:
         self.done[t] = 0
         self.n[t] = 0
         self.out[t].zero_()
+        if self.logprobs is not None:
+            self.lp_n[t] = 0
         if self.sampling:
             self._write_params(t, GREEDY)
         return rescaled
@@ -1237,7 +1283,9 @@ class TenantSession:
         """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
         cache row the token will occupy.  One host read, the one admission makes anyway."""
         if not self.sampling:
-            return torch.argmax(logits, dim=-1).tolist()
+            tok = torch.argmax(logits, dim=-1)
+            self._keep_first_logprobs(logits, tok)
+            return tok.tolist()
         dev = self.dec.dev
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
             logits = logits.contiguous()
@@ -1246,7 +1294,14 @@ class TenantSession:
                               torch.tensor([sp[2] for sp in sps], dtype=torch.float32).to(dev),
                               torch.tensor([sp[3] - (1 << 64) if sp[3] >= 1 << 63 else sp[3] for sp in sps], dtype=torch.long).to(dev),
                               torch.full((len(sps),), int(d), dtype=torch.long).to(dev))
+        self._keep_first_logprobs(logits, tok)
         return tok.tolist()
+
+    def _keep_first_logprobs(self, logits, tok):
+        """a logprob session: the first tokens' entries from the prefill's logits [R, V] and the tokens just chosen, both still on the device;
+        _admit copies row r into the tenant's entry 0.  No host read."""
+        if self.logprobs is not None:
+            self._first_lp = ops.token_logprobs(logits, tok.view(-1), self.logprobs)
 
     def _stops(self, stop_token_ids):
         s_ = sorted(int(i) for i in (stop_token_ids or ()))
@@ -1254,10 +1309,16 @@ class TenantSession:
             raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
         return s_
 
-    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY):
-        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw)"""
+    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0):
+        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw); row: its row of that prefill"""
         if self.sampling:
             self._write_params(t, sp)
+        if self.logprobs is not None:                 # the turn's entries restart with it, as result() does
+            lp, top_id, top_lp = self._first_lp
+            self.lp[t, 0] = lp[row]
+            self.top_id[t, 0] = top_id[row]
+            self.top_lp[t, 0] = top_lp[row]
+            self.lp_n[t] = 1
         reason = (1 if first in stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
         self.stop_ids[t].fill_(-1)
         if stops:
@@ -1341,7 +1402,7 @@ class TenantSession:
             raise ValueError("the padded prompts do not fit the KV cache")
         first = self._first_tokens(dec.prefill(ids, am, self.cache), sps, L)
         for t in range(self.T):
-            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t])
+            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t)
             self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
@@ -1356,17 +1417,20 @@ class TenantSession:
                                 self.temperature, self.top_k, self.top_p, self.seed)
         else:
             ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
+        if self.logprobs is not None:
+            ops.step_logprobs(logits, self.tok, self.n, self.lp_n, self.lp, self.top_id, self.top_lp)
 
     def _state(self):
-        return [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
+        st = [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
+        return st + [self.lp_n] if self.logprobs is not None else st
 
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
-        and the kind of session (greedy or sampling: another last launch) alone."""
+        and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
-               self.sampling)
+               self.sampling, self.logprobs)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:
@@ -1410,3 +1474,13 @@ class TenantSession:
         """(tokens, reason): tenant t's new tokens so far as a 1-D CPU tensor, and why it stopped (0 while it is active)"""
         n = min(int(self.n[t]), self.out.shape[1])
         return self.out[t, :n].cpu(), int(self.done[t])
+
+    def result_logprobs(self, t):
+        """(token_logprobs [n], top_ids [n, k], top_logprobs [n, k]) as CPU tensors (float32, int32, float32) for the n tokens result(t) returns:
+        entry j is token j's log-probability under the model's own distribution -- softmax of the step's logits at temperature 1, before top-k /
+        top-p, whatever the request sampled with -- and the k = session(logprobs=k) most probable tokens of that step with theirs, in descending
+        order (include/bitdelta_hip.h, bd_srv_token_logprobs).  ValueError in a session made without logprobs."""
+        if self.logprobs is None:
+            raise ValueError("this session keeps no log-probabilities: make it with session(logprobs=k), 0 <= k <= %d" % ops.LOGPROBS_MAX)
+        n = min(int(self.n[t]), self.out.shape[1])
+        return self.lp[t, :n].cpu(), self.top_id[t, :n].cpu(), self.top_lp[t, :n].cpu()

@@ -319,6 +319,57 @@ def token_nll(logits, labels, lse=False):
     return (nll, row_lse) if lse else nll
 
 
+LOGPROBS_MAX = 20          # include/bitdelta_hip.h (bd_srv_token_logprobs): top_n is 0 .. 20
+
+
+def token_logprobs(logits, tokens, top_n, out=None):
+    """(lp, top_id, top_lp) for logits [R, V] (16-bit, V % 8 == 0), tokens int64 [R] and 0 <= top_n <= 20: lp[r] = log softmax(logits[r])[tokens[r]]
+    (float32 [R]), top_id int32 / top_lp float32 [R, top_n] the top_n most probable tokens of each row and their log-probabilities, in descending
+    order, ties by ascending index; include/bitdelta_hip.h (bd_srv_token_logprobs) is the definition.  The distribution is the row's softmax at
+    temperature 1, before any filter.  Rows whose layout the entry point does not take (last dimension strided, a row stride that is no multiple
+    of 8, a misaligned start) are copied first; the elements V .. stride - 1 of a row are never read into a result.  out: (lp, top_id, top_lp)
+    to write into instead of new tensors (contiguous, of those shapes and dtypes)."""
+    require_gpu(logits, tokens)
+    assert logits.dim() == 2 and tokens.dtype == torch.long and tokens.numel() == logits.shape[0]
+    R, V = logits.shape
+    top_n = int(top_n)
+    assert V % 8 == 0 and 0 <= top_n <= min(LOGPROBS_MAX, V)
+    sl = logits.stride(0) if R > 1 else V
+    if logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16:
+        logits, sl = logits.contiguous(), V
+    tokens = tokens.contiguous()
+    if out is None:
+        out = (torch.empty(R, dtype=torch.float32, device=logits.device), torch.empty((R, top_n), dtype=torch.int32, device=logits.device),
+               torch.empty((R, top_n), dtype=torch.float32, device=logits.device))
+    lp, top_id, top_lp = out
+    require_gpu(lp, top_id, top_lp)
+    assert lp.dtype == torch.float32 and lp.shape == (R,) and lp.is_contiguous()
+    assert top_id.dtype == torch.int32 and top_id.shape == (R, top_n) and top_id.is_contiguous()
+    assert top_lp.dtype == torch.float32 and top_lp.shape == (R, top_n) and top_lp.is_contiguous()
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_token_logprobs(ptr(logits), sl, V, ptr(tokens), ptr(lp), ptr(top_id) if top_n else None, ptr(top_lp) if top_n else None,
+                                          top_n, R, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_token_logprobs")
+    return lp, top_id, top_lp
+
+
+def step_logprobs(logits, tok, n, lp_n, lp, top_id, top_lp):
+    """Behind step_end_ragged / step_end_sample in the same step, per tenant whose count n[t] moved past lp_n[t]: entry [t, n[t] - 1] of lp
+    [T, cap] float32, top_id [T, cap, k] int32 and top_lp [T, cap, k] float32 from row t of logits [T, V] and tok[t] (token_logprobs' rule), and
+    lp_n[t] = n[t].  A tenant that emitted nothing in the step is not touched.  n / lp_n [T] long; k = top_id.shape[2], 0 .. 20."""
+    require_gpu(logits, tok, n, lp_n, lp, top_id, top_lp)
+    T, V = logits.shape
+    cap, k = top_id.shape[1], top_id.shape[2]
+    assert logits.stride(1) == 1 and V % 8 == 0 and tok.dtype == torch.long and tok.is_contiguous() and tok.numel() == T
+    for v in (n, lp_n):
+        assert v.dtype == torch.long and v.numel() == T and v.is_contiguous()
+    assert lp.dtype == torch.float32 and lp.shape == (T, cap) and lp.is_contiguous()
+    assert top_id.dtype == torch.int32 and top_id.shape == (T, cap, k) and top_id.is_contiguous()
+    assert top_lp.dtype == torch.float32 and top_lp.shape == (T, cap, k) and top_lp.is_contiguous() and 0 <= k <= min(LOGPROBS_MAX, V)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_logprobs(ptr(logits), logits.stride(0), V, ptr(tok), ptr(n), ptr(lp_n), ptr(lp), ptr(top_id) if k else None,
+                                         ptr(top_lp) if k else None, cap, k, T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_logprobs")
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

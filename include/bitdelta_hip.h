@@ -345,6 +345,39 @@ int bd_srv_step_end_sample(const void* logits, int64_t sl, int V, int64_t* tok, 
  * labels or nll NULL -> BD_E_NULL; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE.  One 256-thread block per row; up to V = 32768 the row is read from
  * global memory exactly once and held in registers, a longer row twice. */
 int bd_srv_token_nll(const void* logits, int64_t sl, int V, const int64_t* labels, float* nll, float* lse, int R, int dtype, void* stream);
+/* bd_srv_token_logprobs: what a serving API reports next to a generated token (OpenAI's logprobs / top_logprobs, vLLM's logprobs=): each row of
+ * 16-bit logits, a token y and a count top_n become the token's log-probability and the top_n most probable tokens with theirs.  The
+ * distribution is softmax(row) at temperature 1, before any top-k / top-p filter: the model's own, whatever the request sampled with.
+ *   m, S    exactly bd_srv_token_nll's: m = max_i l_i; per ALIGNED 8-vector the masses exp(l_i - m) summed pairwise in fp32 in a fixed order, the
+ *           vector's sum truncated to 2^-40 fixed point; S the INTEGER sum of those words; ln S = log(double(S) * 2^-40) in fp64 on one thread.
+ *   lp(i)   = float((double(l_i) - double(m)) - ln S): the float negation of bd_srv_token_nll's value on the same row and label (both sums are
+ *           the same fp64 operations with the signs turned), -0 and +0 being one float.
+ *   lp[r]   = lp(tok[r]); a token outside [0, V) gives NaN (a chosen token is never out of range: a NaN there shows the caller's error).
+ *   top_id[r, 0 .. top_n)   the indices of the top_n largest logit VALUES in descending order; equal values -- -0 and +0 are one value -- in
+ *           ascending index order.  The order is that of (key descending, index ascending) with the monotone 16-bit key of the sampling rule.
+ *   top_lp[r, j] = lp(top_id[r, j]).
+ *   -inf    has lp = -inf and enters the list only when fewer than top_n values are finite, and then in index order (the same tie rule).
+ *   A row that holds a NaN or a +inf, or nothing finite: lp = NaN, every top_lp = NaN, every top_id = -1.
+ *   Every output is a pure function of (row, y, top_n): not of R, the row's index, sl, graph or eager execution, or thread order.  No
+ *   floating-point atomics; every cross-thread count or sum that decides a result is an integer.
+ *   Accuracy: bd_srv_token_nll's clause -- every finite lp / top_lp is within 2^-19 (1 + |exact|) of the exact log softmax; the ids are exact.
+ *   tests/logprobs_ref.py restates the definition in fp64.
+ * logits [R, V] fp16 / bf16 with row stride sl (elements); tok int64 [R]; lp fp32 [R]; top_id int32 and top_lp fp32 [R, top_n], contiguous, or
+ * NULL when top_n == 0 (then only lp is computed).  V % 8 == 0, 8 <= V <= 2^22; elements V .. sl - 1 of a row may hold anything and never reach
+ * a result.  Checked before any device call: R == 0 -> BD_OK, nothing launched; top_n outside 0 .. 20, top_n > V, V % 8 != 0, sl % 8 != 0,
+ * sl < V, V > 2^22, R < 0, logits not 16-byte, tok not 8-byte or an output not 4-byte aligned -> BD_E_BAD_SHAPE; a needed pointer NULL ->
+ * BD_E_NULL; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE.  One 256-thread block per row; up to V = 32768 the row is read once and held in registers. */
+int bd_srv_token_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, float* lp, int32_t* top_id, float* top_lp, int top_n,
+                          int R, int dtype, void* stream);
+/* bd_srv_step_logprobs: bd_srv_token_logprobs at the end of a ragged decode step, launched AFTER bd_srv_step_end_ragged / bd_srv_step_end_sample
+ * on the same logits [T, V].  tok int64 [T] is the token the step end has just stored; n int64 [T] its per-tenant token count; lp_n int64 [T]
+ * this launch's own counter; lp fp32 [T, cap]; top_id int32 / top_lp fp32 [T, cap, top_n] (NULL when top_n == 0).  Tenant t with
+ * n[t] == lp_n[t] emitted nothing in this step: nothing of it is read or written.  Otherwise, with j = n[t] - 1: when 0 <= j < cap entry [t, j]
+ * is written from row t and tok[t] by the rule above; in either case lp_n[t] = n[t].  The launch reads no activity flag: a tenant that retired
+ * in this step still gets its last token's entry, an inactive one is not touched.  Checks as above with T for R; n or lp_n NULL -> BD_E_NULL,
+ * not 8-byte aligned or cap < 0 -> BD_E_BAD_SHAPE. */
+int bd_srv_step_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, const int64_t* n, int64_t* lp_n, float* lp, int32_t* top_id,
+                         float* top_lp, int cap, int top_n, int T, int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
