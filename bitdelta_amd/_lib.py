@@ -61,6 +61,8 @@ SIGNATURES = {
     "bd_srv_token_nll": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _ci, _ci, _vp]),
     "bd_srv_token_logprobs": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_step_logprobs": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    "bd_srv_penalize_rows": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "bd_srv_step_penalize": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_rope_kv_append": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_rope": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_decode_attention": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),

@@ -25,6 +25,7 @@
 #include "bd_attn_prefill.h"
 #include "bd_token_nll.h"
 #include "bd_logprobs.h"
+#include "bd_penalize.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2198,4 +2199,43 @@ extern "C" int bd_srv_token_logprobs(const void* logits, int64_t sl, int V, cons
 extern "C" int bd_srv_step_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, const int64_t* n, int64_t* lp_n, float* lp,
                                     int32_t* top_id, float* top_lp, int cap, int top_n, int T, int dtype, void* stream) {
     return token_logprobs_launch(logits, sl, V, tok, n, lp_n, lp, top_id, top_lp, cap, top_n, T, dtype, true, stream);
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// One body for the two entry points: step == false is bd_srv_penalize_rows (R live rows, hist read only), true bd_srv_step_penalize (T tenants).
+static int penalize_launch(const void* logits, int64_t sl, int V, void* out, int64_t so, const int16_t* hist, int64_t sh, const int64_t* tok,
+                           const uint8_t* active, const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int R, int dtype,
+                           bool step, void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (nb < 0 || nb > PEN_BIAS_MAX || R > 65535) return BD_E_BAD_SHAPE;
+    if (!logits || !out || !hist || !pen || (step && (!tok || !active)) || (nb > 0 && (!bias_id || !bias_val))) return BD_E_NULL;
+    if (V % 8 || sl % 8 || so % 8 || sh % 8 || sl < V || so < V || sh < V || !aligned16(logits) || !aligned16(out) || !aligned16(hist) ||
+        !aligned16(pen) || !aligned_to(tok, 8) || !aligned_to(bias_id, 4) || !aligned_to(bias_val, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((V + PEN_BLOCK_ELEMS - 1) / PEN_BLOCK_ELEMS), (unsigned)R);
+#define BD_PEN_LAUNCH(DT, STEP)                                                                                                              \
+    hipLaunchKernelGGL((penalize_kernel<DT, STEP>), grid, dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,                 \
+                       (unsigned short*)out, (long long)so, (unsigned short*)const_cast<int16_t*>(hist), (long long)sh, (const long long*)tok, \
+                       (const unsigned char*)active, pen, (const int*)bias_id, bias_val, nb)
+    if (dtype == BD_BF16) {
+        if (step) BD_PEN_LAUNCH(DT_BF16, true); else BD_PEN_LAUNCH(DT_BF16, false);
+    } else {
+        if (step) BD_PEN_LAUNCH(DT_F16, true); else BD_PEN_LAUNCH(DT_F16, false);
+    }
+#undef BD_PEN_LAUNCH
+    return launch_status();
+}
+
+extern "C" int bd_srv_penalize_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int16_t* hist, int64_t sh,
+                                    const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int R, int dtype, void* stream) {
+    return penalize_launch(logits, sl, V, out, so, hist, sh, nullptr, nullptr, pen, bias_id, bias_val, nb, R, dtype, false, stream);
+}
+
+extern "C" int bd_srv_step_penalize(const void* logits, int64_t sl, int V, void* out, int64_t so, int16_t* hist, int64_t sh, const int64_t* tok,
+                                    const uint8_t* active, const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int T,
+                                    int dtype, void* stream) {
+    return penalize_launch(logits, sl, V, out, so, hist, sh, tok, active, pen, bias_id, bias_val, nb, T, dtype, true, stream);
 }

@@ -17,6 +17,7 @@ running the reference's modules under HF, all of them launch-count / traffic onl
   * the decode step is shape-static (KV cache of fixed length, a key-validity mask, the position held in a device tensor), so it
     is captured once as a hipGraph and replayed: greedy feedback happens on the device, the host only polls the stop flags.
 """
+import collections.abc
 import math
 import operator
 import weakref
@@ -1054,12 +1055,15 @@ class TenantDecoder(nn.Module):
         """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
-    def session(self, max_stop_ids=8, sampling=False, logprobs=None):
+    def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
         request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
         logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
-        (TenantSession.result_logprobs); None, the default, keeps nothing and adds no launch."""
-        return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs)
+        (TenantSession.result_logprobs); None, the default, keeps nothing and adds no launch.
+        penalties=True: every request also carries repetition_penalty / presence_penalty / frequency_penalty / logit_bias (penalty_params; at
+        most max_logit_bias <= 64 bias entries per request); independent of sampling and logprobs.  The default session takes none of them,
+        allocates nothing for them and runs the step it ran before."""
+        return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1139,6 +1143,63 @@ def sampling_params(temperature=0.0, top_k=0, top_p=1.0, seed=0):
 GREEDY = sampling_params()
 
 
+def penalty_params(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, *, vocab=None,
+                   max_logit_bias=ops.LOGIT_BIAS_MAX):
+    """The penalty parameters of one request, validated on the host: (repetition_penalty, presence_penalty, frequency_penalty, bias) as
+    (float, float, float, ((id, value), ...)) with the bias sorted by id -- the canonical form: two requests that mean the same compare equal.
+    repetition_penalty: finite and > 0 (1 = off; HF's rule); presence_penalty / frequency_penalty: finite (0 = off; OpenAI's rule on the tokens
+    generated in this turn); logit_bias: None or a mapping {token id: value} -- integer ids (no bools) in [0, vocab) when the vocabulary size is
+    given, values finite with |value| <= 100, or -inf (the token is banned), at most max_logit_bias entries.  Anything else raises ValueError.
+    The defaults change nothing (NEUTRAL)."""
+    try:
+        r, pres, freq = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    except (TypeError, ValueError):
+        raise ValueError("repetition_penalty = %r, presence_penalty = %r, frequency_penalty = %r: numbers are required"
+                         % (repetition_penalty, presence_penalty, frequency_penalty))
+    if any(isinstance(v, bool) for v in (repetition_penalty, presence_penalty, frequency_penalty)):
+        raise ValueError("a penalty is a number, not a bool")
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError("repetition_penalty = %r: a finite value > 0 is required (1 = off)" % (repetition_penalty,))
+    if not (math.isfinite(pres) and math.isfinite(freq)):
+        raise ValueError("presence_penalty = %r, frequency_penalty = %r: finite values are required (0 = off)"
+                         % (presence_penalty, frequency_penalty))
+    bias = []
+    if logit_bias is not None:
+        if not isinstance(logit_bias, collections.abc.Mapping):
+            raise ValueError("logit_bias = %r: a mapping {token id: value} is required" % (logit_bias,))
+        if len(logit_bias) > max_logit_bias:
+            raise ValueError("logit_bias holds %d entries: at most %d are kept per request" % (len(logit_bias), max_logit_bias))
+        for k, v in logit_bias.items():
+            try:
+                if isinstance(k, bool) or isinstance(v, bool):
+                    raise TypeError
+                i, b = operator.index(k), float(v)
+            except (TypeError, ValueError):
+                raise ValueError("logit_bias[%r] = %r: an integer token id and a number are required" % (k, v))
+            if i < 0 or (vocab is not None and i >= vocab):
+                raise ValueError("logit_bias: token id %d is outside the vocabulary" % i)
+            if not (b == -math.inf or (math.isfinite(b) and abs(b) <= 100.0)):
+                raise ValueError("logit_bias[%d] = %r: a finite value with |value| <= 100, or -inf (a ban), is required" % (i, v))
+            bias.append((i, b))
+        bias.sort()
+    return r, pres, freq, tuple(bias)
+
+
+NEUTRAL = penalty_params()
+
+
+def penalty_row(pp):
+    """the four floats the kernel reads for penalty_params' tuple pp: (r, float32(1 / r) from the fp64 quotient, presence, frequency)"""
+    return [pp[0], 1.0 / pp[0], pp[1], pp[2]]
+
+
+def fold_history(hist):
+    """TenantSession.extend's fold of a history row (int16, any shape; a new tensor): every non-zero element becomes bit 15 alone.  What the
+    earlier turns held or generated is context of the next turn, and the counts restart with the turn, as result() does -- the history a submit
+    of the whole conversation would have written."""
+    return torch.where(hist != 0, torch.full_like(hist, -32768), torch.zeros_like(hist))
+
+
 def logprobs_count(logprobs):
     """The logprobs= argument of a session, validated on the host: None (nothing is kept) or an integer 0 <= k <= 20 (0: the chosen token's
     log-probability only; k: the k most probable alternatives with it).  A bool, a non-integer or a value outside the range raises ValueError."""
@@ -1187,12 +1248,24 @@ class TenantSession:
     entry comes from the prefill's logits on the device.  The count is the session's: it sizes the buffers and the captured graph.  None keeps
     nothing and launches nothing.
 
+    penalties=True: a request carries repetition_penalty / presence_penalty / frequency_penalty / logit_bias (penalty_params;
+    include/bitdelta_hip.h, bd_srv_penalize_rows, defines the penalised row).  The session keeps a token history per tenant (hist [T, V] int16:
+    bit 15 = in the context of this turn, bits 0 .. 14 = times generated in this turn), the parameters and the bias list as device arrays, and
+    one more launch (serving_ops.step_penalize) between the lm_head and the step-end launch counts the token fed in and writes the penalised
+    logits the step end then reads; the first token is chosen from the penalised prefill logits.  Nothing is baked into the captured graph.
+    result_logprobs keeps reporting the RAW logits' distribution.  Without penalties=True the session refuses non-neutral values (ValueError),
+    allocates none of this and launches nothing more.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full; 0 = still active or never submitted."""
 
-    def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None):
+    def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16):
         self.logprobs = logprobs_count(logprobs)
+        self.penalties = bool(penalties)
+        if self.penalties and not (isinstance(max_logit_bias, int) and not isinstance(max_logit_bias, bool)
+                                   and 0 <= max_logit_bias <= ops.LOGIT_BIAS_MAX):
+            raise ValueError("max_logit_bias = %r: an integer 0 .. %d is required" % (max_logit_bias, ops.LOGIT_BIAS_MAX))
         _, _, _, heads, kvh, _ = dec.cfg
         if not (dec.fast_glue and dec.step_kernels):
             raise ValueError("a session runs on the HIP glue and step kernels (fast_glue, step_kernels); there is no stock-op ragged step")
@@ -1228,6 +1301,13 @@ class TenantSession:
             self.lp = torch.zeros(T, cap, dtype=torch.float32, device=dev)
             self.top_id = torch.zeros(T, cap, k, dtype=torch.int32, device=dev)
             self.top_lp = torch.zeros(T, cap, k, dtype=torch.float32, device=dev)
+        if self.penalties:                            # per tenant: token history, (r, 1 / r, presence, frequency), the bias list, the penalised row
+            V = dec.lm_head.shape[-2]
+            self.hist = torch.zeros(T, V, dtype=torch.int16, device=dev)
+            self.pen = torch.tensor([penalty_row(NEUTRAL)] * T, dtype=torch.float32).to(dev)
+            self.bias_id = torch.full((T, max_logit_bias), -1, dtype=torch.int32, device=dev)
+            self.bias_val = torch.zeros(T, max_logit_bias, dtype=torch.float32, device=dev)
+            self.plogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
         self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
@@ -1254,6 +1334,9 @@ class TenantSession:
             self.lp_n[t] = 0
         if self.sampling:
             self._write_params(t, GREEDY)
+        if self.penalties:
+            self.hist[t].zero_()
+            self._write_penalties(t, NEUTRAL)
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -1262,6 +1345,41 @@ class TenantSession:
         if not self.sampling and sp != GREEDY:
             raise ValueError("this session is greedy: make it with session(sampling=True) to pass temperature / top_k / top_p / seed")
         return sp
+
+    def _penalty_params(self, repetition_penalty, presence_penalty, frequency_penalty, logit_bias):
+        """one request's validated penalty parameters; a session made without penalties=True takes the neutral values only"""
+        pp = penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab=self.dec.lm_head.shape[-2],
+                            max_logit_bias=self.bias_id.shape[1] if self.penalties else ops.LOGIT_BIAS_MAX)
+        if not self.penalties and pp != NEUTRAL:
+            raise ValueError("this session takes no penalties: make it with session(penalties=True) to pass repetition_penalty / "
+                             "presence_penalty / frequency_penalty / logit_bias")
+        return pp
+
+    def _write_penalties(self, t, pp):
+        cap = self.bias_id.shape[1]
+        self.pen[t] = torch.tensor(penalty_row(pp), dtype=torch.float32).to(self.dec.dev)
+        if cap:
+            bias = pp[3]
+            self.bias_id[t] = torch.tensor([b[0] for b in bias] + [-1] * (cap - len(bias)), dtype=torch.int32).to(self.dec.dev)
+            self.bias_val[t] = torch.tensor([b[1] for b in bias] + [0.0] * (cap - len(bias)), dtype=torch.float32).to(self.dec.dev)
+
+    def _context(self, t, tokens, pp, fold=False):
+        """a penalty session, before the first token is chosen: tenant t's parameters, and its history -- cleared (submit) or folded (extend:
+        fold_history), then bit 15 set at `tokens`, the real tokens this admission adds to the context.  Torch ops on the current stream, no
+        host read."""
+        if not self.penalties:
+            return
+        self._write_penalties(t, pp)
+        if fold:
+            self.hist[t] = fold_history(self.hist[t])
+        else:
+            self.hist[t].zero_()
+        self.hist[t].index_fill_(0, torch.tensor(tokens, dtype=torch.long).to(self.dec.dev), -32768)
+
+    def _check_tokens(self, tokens):
+        """a penalty session indexes its history with the request's tokens: ids outside the vocabulary are refused on the host"""
+        if self.penalties and not all(0 <= int(i) < self.hist.shape[1] for i in tokens):
+            raise ValueError("a token id is outside the vocabulary")
 
     def _per_tenant(self, v):
         if isinstance(v, torch.Tensor):
@@ -1279,12 +1397,17 @@ class TenantSession:
         self.top_p[t] = p
         self.seed[t] = s_ - (1 << 64) if s_ >= 1 << 63 else s_
 
-    def _first_tokens(self, logits, sps, d):
+    def _first_tokens(self, logits, sps, d, rows=slice(None)):
         """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
-        cache row the token will occupy.  One host read, the one admission makes anyway."""
+        cache row the token will occupy.  One host read, the one admission makes anyway.  rows: the tenants the R rows belong to; a penalty
+        session chooses from their penalised rows (serving_ops.penalize_rows on the history and parameters _context has just written), and
+        its log-probabilities are still the raw rows'."""
+        raw = logits
+        if self.penalties:
+            logits = ops.penalize_rows(logits, self.hist[rows], self.pen[rows], self.bias_id[rows], self.bias_val[rows])
         if not self.sampling:
             tok = torch.argmax(logits, dim=-1)
-            self._keep_first_logprobs(logits, tok)
+            self._keep_first_logprobs(raw, tok)
             return tok.tolist()
         dev = self.dec.dev
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
@@ -1294,7 +1417,7 @@ class TenantSession:
                               torch.tensor([sp[2] for sp in sps], dtype=torch.float32).to(dev),
                               torch.tensor([sp[3] - (1 << 64) if sp[3] >= 1 << 63 else sp[3] for sp in sps], dtype=torch.long).to(dev),
                               torch.full((len(sps),), int(d), dtype=torch.long).to(dev))
-        self._keep_first_logprobs(logits, tok)
+        self._keep_first_logprobs(raw, tok)
         return tok.tolist()
 
     def _keep_first_logprobs(self, logits, tok):
@@ -1333,14 +1456,18 @@ class TenantSession:
         self.active_flags[t] = reason == 0
 
     @torch.no_grad()
-    def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
         alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
-        session(sampling=True); the first token's draw index is the padded length L."""
+        session(sampling=True); the first token's draw index is the padded length L.  repetition_penalty / presence_penalty /
+        frequency_penalty / logit_bias: penalty_params, in a session(penalties=True); the context of the turn is the prompt's real tokens."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
         sp = self._params(temperature, top_k, top_p, seed)
+        pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        self._check_tokens(prompt)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
         L = padded_length(len(prompt))
@@ -1354,11 +1481,13 @@ class TenantSession:
         ids[0, L - len(prompt):] = torch.tensor(prompt, dtype=torch.long)
         am[0, L - len(prompt):] = True
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
-        self._admit(t, int(self._first_tokens(logits, [sp], L)[0]), L, max_new_tokens, stops, sp)
+        self._context(t, prompt, pp)
+        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
-    def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -1370,7 +1499,8 @@ class TenantSession:
         prefill (tenant t's activity flag, position, stop reason and last token together) and, as in submit, one of the first token after it.
         The conversation is the decoder's cache rows: a generate() on the decoder ends it
         without the session knowing.  temperature / top_k / top_p / seed as in submit (this turn's own; invalid ones raise ValueError before
-        anything is touched); the first token's draw index is P + n."""
+        anything is touched); the first token's draw index is P + n.  The penalty arguments as in submit (this turn's own); the turn's context is
+        everything the conversation held before it plus [last emitted token] + tokens, and its counts start at zero (fold_history)."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
@@ -1378,21 +1508,30 @@ class TenantSession:
         tokens = [int(i) for i in tokens]
         stops = self._stops(stop_token_ids)
         sp = self._params(temperature, top_k, top_p, seed)
+        pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
         ids = torch.tensor([[last] + tokens], dtype=torch.long).to(dec.dev)
         kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
-        self._admit(t, int(self._first_tokens(logits, [sp], P + n)[0]), P + n, max_new_tokens, stops, sp)
+        self._context(t, [last] + tokens, pp, fold=True)
+        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp)
 
     @torch.no_grad()
-    def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+    def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
+                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
-        common padded length.  temperature / top_k / top_p / seed: each a scalar or one value per tenant."""
+        common padded length.  temperature / top_k / top_p / seed and the four penalty arguments: each one value for all (a logit_bias mapping
+        is one value) or a list with one value per tenant."""
         dec = self.dec
         assert max_new_tokens >= 1
         sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
                                              self._per_tenant(seed))]
+        pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
+                                                     self._per_tenant(frequency_penalty), self._per_tenant(logit_bias))]
+        for p_ in prompts:
+            self._check_tokens(p_)
         if bool(self.active_flags.any()):
             raise RuntimeError("a tenant is still generating")
         stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
@@ -1400,7 +1539,10 @@ class TenantSession:
         L = ids.shape[1]
         if L > self.Lc:
             raise ValueError("the padded prompts do not fit the KV cache")
-        first = self._first_tokens(dec.prefill(ids, am, self.cache), sps, L)
+        logits = dec.prefill(ids, am, self.cache)
+        for t in range(self.T):
+            self._context(t, prompts[t], pps[t])
+        first = self._first_tokens(logits, sps, L)
         for t in range(self.T):
             self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t)
             self._kv_start[t] = L - len(prompts[t])
@@ -1412,25 +1554,33 @@ class TenantSession:
         logits = dec.forward(self.tok, None, self.cache, None, x=x, ragged=(self.pos, self.active_flags))
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
             raise RuntimeError("the lm_head output is not laid out for the step kernel (16-byte aligned rows)")
+        raw = logits                                  # (step_logprobs keeps reading the model's own row)
+        if self.penalties:                            # counts the token fed in, writes the row the step end chooses from
+            logits = ops.step_penalize(raw, self.plogits, self.hist, self.tok, self.active_flags, self.pen, self.bias_id, self.bias_val)
         if self.sampling:
             ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
                                 self.temperature, self.top_k, self.top_p, self.seed)
         else:
             ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
         if self.logprobs is not None:
-            ops.step_logprobs(logits, self.tok, self.n, self.lp_n, self.lp, self.top_id, self.top_lp)
+            ops.step_logprobs(raw, self.tok, self.n, self.lp_n, self.lp, self.top_id, self.top_lp)
 
     def _state(self):
         st = [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
-        return st + [self.lp_n] if self.logprobs is not None else st
+        if self.logprobs is not None:
+            st = st + [self.lp_n]
+        if self.penalties:                            # (the warm-up and the capture step would count their token twice otherwise)
+            st = st + [self.hist]
+        return st
 
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
-        and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers) alone."""
+        and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
+        one more launch in front of the last) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
-               self.sampling, self.logprobs)
+               self.sampling, self.logprobs, self.penalties)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:
@@ -1479,7 +1629,9 @@ class TenantSession:
         """(token_logprobs [n], top_ids [n, k], top_logprobs [n, k]) as CPU tensors (float32, int32, float32) for the n tokens result(t) returns:
         entry j is token j's log-probability under the model's own distribution -- softmax of the step's logits at temperature 1, before top-k /
         top-p, whatever the request sampled with -- and the k = session(logprobs=k) most probable tokens of that step with theirs, in descending
-        order (include/bitdelta_hip.h, bd_srv_token_logprobs).  ValueError in a session made without logprobs."""
+        order (include/bitdelta_hip.h, bd_srv_token_logprobs).  In a session(penalties=True) too the entries are computed from the RAW logits of
+        the step, not from the penalised row the token was chosen from: a banned token keeps its model probability, and a token forced by a bias
+        is reported with the probability the model gave it.  ValueError in a session made without logprobs."""
         if self.logprobs is None:
             raise ValueError("this session keeps no log-probabilities: make it with session(logprobs=k), 0 <= k <= %d" % ops.LOGPROBS_MAX)
         n = min(int(self.n[t]), self.out.shape[1])

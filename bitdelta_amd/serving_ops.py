@@ -370,6 +370,63 @@ def step_logprobs(logits, tok, n, lp_n, lp, top_id, top_lp):
                                          ptr(top_lp) if k else None, cap, k, T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_logprobs")
 
 
+LOGIT_BIAS_MAX = 64        # include/bitdelta_hip.h (BD_LOGIT_BIAS_MAX): pairs per row of a bias list
+
+
+def _penalty_args(logits, out, hist, pen, bias_id, bias_val):
+    """the checks penalize_rows and step_penalize share; returns (out, nb, bias_id pointer, bias_val pointer)"""
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and logits.dtype in (torch.float16, torch.bfloat16)
+    if out is None:
+        out = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
+    require_gpu(out, hist, pen)
+    assert out.shape == (R, V) and out.dtype == logits.dtype and out.stride(1) == 1
+    assert hist.shape == (R, V) and hist.dtype == torch.int16 and hist.stride(1) == 1
+    assert pen.shape == (R, 4) and pen.dtype == torch.float32 and pen.is_contiguous()
+    if bias_id is None or bias_id.shape[1] == 0:
+        return out, 0, None, None
+    require_gpu(bias_id, bias_val)
+    nb = bias_id.shape[1]
+    assert bias_id.shape == bias_val.shape == (R, nb) and nb <= LOGIT_BIAS_MAX and bias_id.is_contiguous() and bias_val.is_contiguous()
+    assert bias_id.dtype == torch.int32 and bias_val.dtype == torch.float32
+    return out, nb, ptr(bias_id), ptr(bias_val)
+
+
+def penalize_rows(logits, hist, pen, bias_id=None, bias_val=None, out=None):
+    """The penalised copy of logits [R, V] (16-bit, V % 8 == 0): repetition / presence / frequency penalties from the rows' token history hist
+    int16 [R, V] (bit 15: in the context; bits 0 .. 14: times generated this turn) and pen float32 [R, 4] = (r, float(1 / r), presence,
+    frequency), then the bias list bias_id int32 / bias_val float32 [R, nb <= 64] (id -1: an empty slot; None: no list), rounded to the logits'
+    dtype; include/bitdelta_hip.h (bd_srv_penalize_rows) is the definition.  Every row is live and hist is only read.  Rows may be strided
+    (stride % 8 == 0, 16-byte aligned; logits of another layout are copied first, as in token_logprobs); out: a tensor of the logits' shape
+    and dtype to write into instead of a new one."""
+    require_gpu(logits)
+    assert logits.dim() == 2
+    R, V = logits.shape
+    sl = logits.stride(0) if R > 1 else V
+    if logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16:             # (token_logprobs' rule: such rows are copied first)
+        logits, sl = logits.contiguous(), V
+    out, nb, bi, bv = _penalty_args(logits, out, hist, pen, bias_id, bias_val)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_penalize_rows(ptr(logits), sl, V, ptr(out), out.stride(0) if R > 1 else V, ptr(hist), hist.stride(0) if R > 1 else V,
+                                         ptr(pen), bi, bv, nb, R, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_penalize_rows")
+    return out
+
+
+def step_penalize(logits, out, hist, tok, active, pen, bias_id=None, bias_val=None):
+    """penalize_rows inside a ragged decode step, logits [T, V] -> out [T, V], and it counts: for an active tenant t the element tok[t] (the token
+    generated last and fed in this step) of hist [T, V] gains one (saturating at 32767) before the penalties read it, and that one element is
+    stored.  An inactive tenant's rows of out and hist are not touched.  tok [T] or [T, 1] long, active [T] bool / uint8."""
+    require_gpu(logits, tok, active)
+    out, nb, bi, bv = _penalty_args(logits, out, hist, pen, bias_id, bias_val)
+    T, V = logits.shape
+    assert tok.dtype == torch.long and tok.is_contiguous() and tok.numel() == T
+    assert active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == T
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_penalize(ptr(logits), logits.stride(0), V, ptr(out), out.stride(0), ptr(hist), hist.stride(0), ptr(tok), ptr(active),
+                                         ptr(pen), bi, bv, nb, T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_penalize")
+    return out
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

@@ -378,6 +378,48 @@ int bd_srv_token_logprobs(const void* logits, int64_t sl, int V, const int64_t* 
  * not 8-byte aligned or cap < 0 -> BD_E_BAD_SHAPE. */
 int bd_srv_step_logprobs(const void* logits, int64_t sl, int V, const int64_t* tok, const int64_t* n, int64_t* lp_n, float* lp, int32_t* top_id,
                          float* top_lp, int cap, int top_n, int T, int dtype, void* stream);
+/* bd_srv_penalize_rows: the controls a serving API carries next to temperature / top-k / top-p (HF's repetition_penalty, OpenAI's
+ * presence_penalty / frequency_penalty / logit_bias, vLLM's SamplingParams): each row of 16-bit logits, the row's token history, four floats
+ * and a short bias list become the penalised row in the logits' dtype, which the token choice (argmax, bd_srv_sample_rows, the step-end
+ * launches) then reads in place of the raw one.
+ *   hist[v] (int16, read as raw bits): bit 15 = token v occurs in the context of this turn (the real prompt tokens, never the left pads; after
+ *           an extension everything the conversation held before the turn plus the new chunk); bits 0 .. 14 = c, the number of times v has been
+ *           generated and fed back in THIS turn, saturating at 32767.  seen = hist[v] != 0.
+ *   pen     = (r, r_inv, presence, frequency), r_inv = float(1.0 / r) computed by the host in fp64: the kernel never divides.
+ *   bias    nb pairs (bias_id[j], bias_val[j]); an empty slot holds id -1.
+ * For every v in [0, V), in fp32, every operation rounded on its own (no fma contraction):
+ *   x = float(l[v])
+ *   if seen and 0 < r < inf:   x = (x > 0) ? x * r_inv : x * r             (HF's RepetitionPenaltyLogitsProcessor, with the host's reciprocal)
+ *   x = x - frequency * float(c)                                            (one product, one subtraction)
+ *   if c > 0:                  x = x - presence
+ *   for j = 0 .. nb - 1, in list order:   if bias_id[j] == v:  x = x + bias_val[j]      (a repeated id is added twice; -inf bans the token)
+ *   out[v] = x rounded to nearest even to the logits' dtype
+ * The 16-bit rounding is the loss HF takes when its processors penalise logits held in the model's dtype; the token choice reads 16-bit rows.
+ * Device values the host could not have written are neutralised (bd_srv_sample_rows' rule): r that is not in (0, inf), a NaN included, turns
+ * the repetition step off; a NaN presence / frequency counts as 0; a bias_id outside [0, V) matches nothing.
+ * Neutral parameters (r = 1, presence = frequency = 0, nb = 0) reproduce the input bits: x * 1, x - 0 * c and x - 0 are exact and keep -0,
+ * +-inf and subnormals (a NaN stays a NaN).  An out element is a pure function of (l[v], hist[v], pen, bias list): no atomics, nothing depends
+ * on thread or block order, on R, on the strides, or on graph or eager execution.  tests/penalty_ref.py restates the definition.
+ * logits / out [R, V] fp16 / bf16 with row strides sl / so, hist int16 [R, V] with row stride sh (elements); pen fp32 [R, 4]; bias_id int32 and
+ * bias_val fp32 [R, nb], contiguous, NULL allowed only when nb == 0.  Elements V .. stride - 1 of a row are neither read nor written.  Every
+ * row is live and hist is only read.  Checked before any device call, in this order: R < 0, V < 1, V > 2^22 -> BD_E_BAD_SHAPE; dtype not fp16 /
+ * bf16 -> BD_E_BAD_DTYPE; R == 0 -> BD_OK, nothing launched; nb outside 0 .. BD_LOGIT_BIAS_MAX or R > 65535 -> BD_E_BAD_SHAPE; a needed pointer
+ * NULL -> BD_E_NULL; V % 8, a stride % 8 or < V, logits / out / hist / pen not 16-byte or a bias array not 4-byte aligned -> BD_E_BAD_SHAPE.
+ * Several blocks per row: grid (ceil(V / 2048), R), one 16-byte vector of logits and of hist per thread, no LDS, no barrier. */
+#define BD_LOGIT_BIAS_MAX 64
+int bd_srv_penalize_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int16_t* hist, int64_t sh, const float* pen,
+                         const int32_t* bias_id, const float* bias_val, int nb, int R, int dtype, void* stream);
+/* bd_srv_step_penalize: bd_srv_penalize_rows inside a ragged decode step, between the lm_head and bd_srv_step_end_ragged /
+ * bd_srv_step_end_sample (which then read `out`), and it COUNTS: tok int64 [T] is the token generated last and fed in this step, active bytes
+ * [T].  For an active tenant t the element v == tok[t] is first counted -- c = min(count(hist[t, v]) + 1, 32767), and it is seen -- and the
+ * rule above runs with that c; the thread that owns the element stores the new hist[t, v] (bit 15 kept) with one 2-byte store.  No other
+ * element of hist is written; a tok[t] outside [0, V) counts nothing.  So a turn's first token is counted by the turn's first step and the last
+ * token a tenant emits is never counted.  An inactive tenant's hist row and out row are not touched, nothing of it is read.  out[t, v] is a pure
+ * function of (l[v], hist[v], tok[t] == v, pen, bias list).  Checks as above with T for R; tok or active NULL -> BD_E_NULL, tok not 8-byte
+ * aligned -> BD_E_BAD_SHAPE. */
+int bd_srv_step_penalize(const void* logits, int64_t sl, int V, void* out, int64_t so, int16_t* hist, int64_t sh, const int64_t* tok,
+                         const uint8_t* active, const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int T, int dtype,
+                         void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
