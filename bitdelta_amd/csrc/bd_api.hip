@@ -26,6 +26,7 @@
 #include "bd_token_nll.h"
 #include "bd_logprobs.h"
 #include "bd_penalize.h"
+#include "bd_constrain.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2238,4 +2239,60 @@ extern "C" int bd_srv_step_penalize(const void* logits, int64_t sl, int V, void*
                                     const uint8_t* active, const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int T,
                                     int dtype, void* stream) {
     return penalize_launch(logits, sl, V, out, so, hist, sh, tok, active, pen, bias_id, bias_val, nb, T, dtype, true, stream);
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// One body for the two mask entry points: step == false is bd_srv_constrain_rows (R live rows), true bd_srv_step_constrain (T tenants).
+static int constrain_launch(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* state, const int32_t* off,
+                            const int32_t* edge_tok, const uint8_t* accepting, int S, int E, const int64_t* stop_ids, int ns,
+                            const uint8_t* active, int R, int dtype, bool step, void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (S < 1 || S > CON_STATES_MAX || E < 0 || E > CON_EDGES_MAX || ns < 0 || ns > CON_STOP_MAX || R > 65535) return BD_E_BAD_SHAPE;
+    if (!logits || !out || !state || !off || !accepting || (E > 0 && !edge_tok) || (ns > 0 && !stop_ids) || (step && !active)) return BD_E_NULL;
+    if (V % 8 || sl % 8 || so % 8 || sl < V || so < V || !aligned16(logits) || !aligned16(out) || !aligned_to(state, 4) || !aligned_to(off, 4) ||
+        !aligned_to(edge_tok, 4) || !aligned_to(stop_ids, 8))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((V + CON_BLOCK_ELEMS - 1) / CON_BLOCK_ELEMS), (unsigned)R);
+#define BD_CON_LAUNCH(DT, STEP)                                                                                                           \
+    hipLaunchKernelGGL((constrain_kernel<DT, STEP>), grid, dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,              \
+                       (unsigned short*)out, (long long)so, (const int*)state, (const int*)off, (const int*)edge_tok,                      \
+                       (const unsigned char*)accepting, S, E, (const long long*)stop_ids, ns, (const unsigned char*)active)
+    if (dtype == BD_BF16) {
+        if (step) BD_CON_LAUNCH(DT_BF16, true); else BD_CON_LAUNCH(DT_BF16, false);
+    } else {
+        if (step) BD_CON_LAUNCH(DT_F16, true); else BD_CON_LAUNCH(DT_F16, false);
+    }
+#undef BD_CON_LAUNCH
+    return launch_status();
+}
+
+extern "C" int bd_srv_constrain_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* state, const int32_t* off,
+                                     const int32_t* edge_tok, const uint8_t* accepting, int S, int E, const int64_t* stop_ids, int ns, int R,
+                                     int dtype, void* stream) {
+    return constrain_launch(logits, sl, V, out, so, state, off, edge_tok, accepting, S, E, stop_ids, ns, nullptr, R, dtype, false, stream);
+}
+
+extern "C" int bd_srv_step_constrain(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* state, const int32_t* off,
+                                     const int32_t* edge_tok, const uint8_t* accepting, int S, int E, const int64_t* stop_ids, int ns,
+                                     const uint8_t* active, int T, int dtype, void* stream) {
+    return constrain_launch(logits, sl, V, out, so, state, off, edge_tok, accepting, S, E, stop_ids, ns, active, T, dtype, true, stream);
+}
+
+extern "C" int bd_srv_step_constrain_advance(const int64_t* tok, const int64_t* n, int64_t* c_n, int32_t* state, const int32_t* off,
+                                             const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* accepting, int S, int E,
+                                             uint8_t* active, uint8_t* done, int T, void* stream) {
+    if (T < 0) return BD_E_BAD_SHAPE;
+    if (T == 0) return BD_OK;
+    if (S < 1 || S > CON_STATES_MAX || E < 0 || E > CON_EDGES_MAX || T > CON_ADVANCE_T_MAX) return BD_E_BAD_SHAPE;
+    if (!tok || !n || !c_n || !state || !off || !accepting || !active || !done || (E > 0 && (!edge_tok || !edge_next))) return BD_E_NULL;
+    if (!aligned_to(tok, 8) || !aligned_to(n, 8) || !aligned_to(c_n, 8) || !aligned_to(state, 4) || !aligned_to(off, 4) ||
+        !aligned_to(edge_tok, 4) || !aligned_to(edge_next, 4))
+        return BD_E_BAD_SHAPE;
+    hipLaunchKernelGGL((constrain_advance_kernel<CON_ADVANCE_T_MAX>), dim3(1), dim3((unsigned)((T + 63) / 64 * 64)), 0, (hipStream_t)stream, (const long long*)tok,
+                       (const long long*)n, (long long*)c_n, (int*)state, (const int*)off, (const int*)edge_tok, (const int*)edge_next,
+                       (const unsigned char*)accepting, S, E, (unsigned char*)active, (unsigned char*)done, T);
+    return launch_status();
 }

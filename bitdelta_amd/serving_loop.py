@@ -32,6 +32,7 @@ from ._lib import require_gpu
 from .quant import (cat_gptq4, dequantize_base_gptq4, dequantize_base_int8, pack_gptq4_params, quantize_base_gptq4, quantize_base_int8,
                     tile_weight_gptq4, tile_weight_int8, weight_scale)
 from .diff import binarize
+from .constraint import TokenAutomaton
 from . import serving_ops as ops
 
 MODEL_CONFIGS = {
@@ -1055,15 +1056,20 @@ class TenantDecoder(nn.Module):
         """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
-    def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16):
+    def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
+                max_constraint_states=256, max_constraint_edges=4096):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
         request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
         logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
         (TenantSession.result_logprobs); None, the default, keeps nothing and adds no launch.
         penalties=True: every request also carries repetition_penalty / presence_penalty / frequency_penalty / logit_bias (penalty_params; at
         most max_logit_bias <= 64 bias entries per request); independent of sampling and logprobs.  The default session takes none of them,
-        allocates nothing for them and runs the step it ran before."""
-        return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias)
+        allocates nothing for them and runs the step it ran before.
+        constraints=True: every request may also carry constraint= a TokenAutomaton (constraint.py) of at most max_constraint_states states and
+        max_constraint_edges edges, which restricts what the request may emit; independent of the other three.  The default session refuses
+        one, allocates nothing for it and runs the step it ran before."""
+        return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias,
+                             constraints=constraints, max_constraint_states=max_constraint_states, max_constraint_edges=max_constraint_edges)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1256,13 +1262,36 @@ class TenantSession:
     result_logprobs keeps reporting the RAW logits' distribution.  Without penalties=True the session refuses non-neutral values (ValueError),
     allocates none of this and launches nothing more.
 
+    constraints=True: a request may carry constraint= a TokenAutomaton (constraint.py; include/bitdelta_hip.h, bd_srv_constrain_rows, defines the
+    masked row), and every token it emits follows the automaton from its start state.  The session keeps, per tenant, the automaton at fixed
+    sizes (c_off [T, S + 1], c_tok / c_next [T, E], c_acc [T, S]; S = max_constraint_states, E = max_constraint_edges), the current state
+    (c_state [T] int32, -1 = no constraint) and the advance launch's own counter (c_n [T]) as device arrays written at admission, and the step
+    gains two launches: serving_ops.step_constrain between the lm_head (or step_penalize, whose row it then reads) and the step end writes
+    clogits [T, V] -- -inf wherever the tenant's state does not allow the token, the same bits elsewhere -- which the step end reads;
+    serving_ops.step_constrain_advance behind the step end (and step_logprobs) follows the chosen token, and a tenant that reaches a FINAL state
+    (accepting, no edges) retires in that same step with reason 8.  In an accepting state the request's own stop ids are allowed too, and
+    emitting one is reason 1 as ever.  The first token is chosen from serving_ops.constrain_rows of the (penalised) prefill logits in the start
+    state, and the state is advanced once on the host with that token, which admission reads anyway.  extend constrains the new turn only.
+    Nothing is baked into the captured graph.  result_logprobs keeps reporting the RAW logits' distribution.  Without constraints=True the
+    session refuses a constraint (ValueError), allocates none of this and launches nothing more.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
-    reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full; 0 = still active or never submitted."""
+    reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full, 8 = the constraint is complete (a final state
+    of the request's automaton was reached); 0 = still active or never submitted."""
 
-    def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16):
+    def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
+                 max_constraint_states=256, max_constraint_edges=4096):
         self.logprobs = logprobs_count(logprobs)
         self.penalties = bool(penalties)
+        self.constraints = bool(constraints)
+        if self.constraints:
+            for v, what, top in ((max_constraint_states, "max_constraint_states", ops.CONSTRAINT_STATES_MAX),
+                                 (max_constraint_edges, "max_constraint_edges", ops.CONSTRAINT_EDGES_MAX)):
+                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
+                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
+            if max(int(max_stop_ids), 1) > ops.CONSTRAINT_STOP_MAX:
+                raise ValueError("a session with constraints holds at most %d stop ids per request" % ops.CONSTRAINT_STOP_MAX)
         if self.penalties and not (isinstance(max_logit_bias, int) and not isinstance(max_logit_bias, bool)
                                    and 0 <= max_logit_bias <= ops.LOGIT_BIAS_MAX):
             raise ValueError("max_logit_bias = %r: an integer 0 .. %d is required" % (max_logit_bias, ops.LOGIT_BIAS_MAX))
@@ -1308,6 +1337,15 @@ class TenantSession:
             self.bias_id = torch.full((T, max_logit_bias), -1, dtype=torch.int32, device=dev)
             self.bias_val = torch.zeros(T, max_logit_bias, dtype=torch.float32, device=dev)
             self.plogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+        if self.constraints:                          # per tenant: the automaton at the session's sizes, its state, the advance launch's counter, the masked row
+            V, S, E = dec.lm_head.shape[-2], max_constraint_states, max_constraint_edges
+            self.c_state = torch.full((T,), -1, dtype=torch.int32, device=dev)
+            self.c_n = torch.zeros(T, dtype=torch.long, device=dev)           # step_constrain_advance's own counter: follows n
+            self.c_off = torch.zeros(T, S + 1, dtype=torch.int32, device=dev)
+            self.c_tok = torch.zeros(T, E, dtype=torch.int32, device=dev)
+            self.c_next = torch.zeros(T, E, dtype=torch.int32, device=dev)
+            self.c_acc = torch.zeros(T, S, dtype=torch.uint8, device=dev)
+            self.clogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
         self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
@@ -1337,6 +1375,9 @@ class TenantSession:
         if self.penalties:
             self.hist[t].zero_()
             self._write_penalties(t, NEUTRAL)
+        if self.constraints:
+            self.c_state[t] = -1
+            self.c_n[t] = 0
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -1354,6 +1395,43 @@ class TenantSession:
             raise ValueError("this session takes no penalties: make it with session(penalties=True) to pass repetition_penalty / "
                              "presence_penalty / frequency_penalty / logit_bias")
         return pp
+
+    def _constraint_arg(self, constraint):
+        """a request's constraint= argument: None or a TokenAutomaton; a session made without constraints=True takes None only"""
+        if constraint is None:
+            return None
+        if not self.constraints:
+            raise ValueError("this session takes no constraint: make it with session(constraints=True) to pass constraint=")
+        if not isinstance(constraint, TokenAutomaton):
+            raise ValueError("constraint = %r: None or a TokenAutomaton is required" % (constraint,))
+        return constraint
+
+    def _check_constraint(self, con, stops):
+        """the checks that need the session's sizes and the request's stop ids (TokenAutomaton.check), before anything is touched"""
+        if con is not None:
+            con.check(self.dec.lm_head.shape[-2], self.c_acc.shape[1], self.c_tok.shape[1], bool(stops))
+        return con
+
+    def _write_constraint(self, t, con, stops):
+        """a constraint session, before the first token is chosen: the automaton into tenant t's slices (the rest of them is never indexed: every
+        offset and target lies inside what is written), the start state or -1, and the stop ids the start state may allow.  Torch ops on the
+        current stream, no host read."""
+        if not self.constraints:
+            return
+        dev = self.dec.dev
+        self.stop_ids[t].fill_(-1)                    # (_admit writes the same values again)
+        if stops:
+            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long).to(dev)
+        if con is None:
+            self.c_state[t] = -1
+            return
+        S, E = con.n_states, con.n_edges
+        self.c_off[t, :S + 1] = torch.tensor(con.off, dtype=torch.int32).to(dev)
+        if E:
+            self.c_tok[t, :E] = torch.tensor(con.edge_tok, dtype=torch.int32).to(dev)
+            self.c_next[t, :E] = torch.tensor(con.edge_next, dtype=torch.int32).to(dev)
+        self.c_acc[t, :S] = torch.tensor(con.accepting, dtype=torch.uint8).to(dev)
+        self.c_state[t] = 0
 
     def _write_penalties(self, t, pp):
         cap = self.bias_id.shape[1]
@@ -1400,11 +1478,15 @@ class TenantSession:
     def _first_tokens(self, logits, sps, d, rows=slice(None)):
         """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
         cache row the token will occupy.  One host read, the one admission makes anyway.  rows: the tenants the R rows belong to; a penalty
-        session chooses from their penalised rows (serving_ops.penalize_rows on the history and parameters _context has just written), and
-        its log-probabilities are still the raw rows'."""
+        session chooses from their penalised rows (serving_ops.penalize_rows on the history and parameters _context has just written), a
+        constraint session from those rows masked by the start states _write_constraint has just written (serving_ops.constrain_rows), and
+        the log-probabilities are still the raw rows'."""
         raw = logits
         if self.penalties:
             logits = ops.penalize_rows(logits, self.hist[rows], self.pen[rows], self.bias_id[rows], self.bias_val[rows])
+        if self.constraints:
+            logits = ops.constrain_rows(logits, self.c_state[rows].contiguous(), self.c_off[rows].contiguous(), self.c_tok[rows].contiguous(),
+                                        self.c_acc[rows].contiguous(), self.stop_ids[rows].contiguous())
         if not self.sampling:
             tok = torch.argmax(logits, dim=-1)
             self._keep_first_logprobs(raw, tok)
@@ -1432,8 +1514,9 @@ class TenantSession:
             raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
         return s_
 
-    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0):
-        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw); row: its row of that prefill"""
+    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0, con=None):
+        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw); row: its row of that prefill;
+        con: the request's automaton, advanced here once, on the host, with that first token"""
         if self.sampling:
             self._write_params(t, sp)
         if self.logprobs is not None:                 # the turn's entries restart with it, as result() does
@@ -1443,6 +1526,12 @@ class TenantSession:
             self.top_lp[t, 0] = top_lp[row]
             self.lp_n[t] = 1
         reason = (1 if first in stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
+        if self.constraints:
+            self.c_n[t] = 1
+            if con is not None:
+                s_ = con.step(0, first)
+                self.c_state[t] = s_
+                reason |= 8 if con.is_final(s_) else 0
         self.stop_ids[t].fill_(-1)
         if stops:
             self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long, device=self.dec.dev)
@@ -1457,16 +1546,19 @@ class TenantSession:
 
     @torch.no_grad()
     def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
         alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
         session(sampling=True); the first token's draw index is the padded length L.  repetition_penalty / presence_penalty /
-        frequency_penalty / logit_bias: penalty_params, in a session(penalties=True); the context of the turn is the prompt's real tokens."""
+        frequency_penalty / logit_bias: penalty_params, in a session(penalties=True); the context of the turn is the prompt's real tokens.
+        constraint: None or a TokenAutomaton, in a session(constraints=True): every token of the turn follows it from its start state; refused
+        (ValueError, before anything is touched) when it does not fit the session's sizes or the vocabulary (TokenAutomaton.check)."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
         sp = self._params(temperature, top_k, top_p, seed)
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        con = self._constraint_arg(constraint)
         self._check_tokens(prompt)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
@@ -1476,18 +1568,20 @@ class TenantSession:
         if L > self.Lc:
             raise ValueError("the padded prompt does not fit the KV cache")
         stops = self._stops(stop_token_ids)
+        self._check_constraint(con, stops)
         ids = torch.zeros(1, L, dtype=torch.long)
         am = torch.zeros(1, L, dtype=torch.bool)
         ids[0, L - len(prompt):] = torch.tensor(prompt, dtype=torch.long)
         am[0, L - len(prompt):] = True
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
         self._context(t, prompt, pp)
-        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp)
+        self._write_constraint(t, con, stops)
+        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
     def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -1500,7 +1594,8 @@ class TenantSession:
         The conversation is the decoder's cache rows: a generate() on the decoder ends it
         without the session knowing.  temperature / top_k / top_p / seed as in submit (this turn's own; invalid ones raise ValueError before
         anything is touched); the first token's draw index is P + n.  The penalty arguments as in submit (this turn's own); the turn's context is
-        everything the conversation held before it plus [last emitted token] + tokens, and its counts start at zero (fold_history)."""
+        everything the conversation held before it plus [last emitted token] + tokens, and its counts start at zero (fold_history).
+        constraint as in submit: it constrains THIS turn's tokens only, from its start state; None leaves the turn free."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
@@ -1509,6 +1604,7 @@ class TenantSession:
         stops = self._stops(stop_token_ids)
         sp = self._params(temperature, top_k, top_p, seed)
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+        con = self._check_constraint(self._constraint_arg(constraint), stops)
         self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
@@ -1516,25 +1612,30 @@ class TenantSession:
         kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
         self._context(t, [last] + tokens, pp, fold=True)
-        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp)
+        self._write_constraint(t, con, stops)
+        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
+                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
         common padded length.  temperature / top_k / top_p / seed and the four penalty arguments: each one value for all (a logit_bias mapping
-        is one value) or a list with one value per tenant."""
+        is one value) or a list with one value per tenant.  constraint: None or one TokenAutomaton for all, or a list with one (or None) per
+        tenant."""
         dec = self.dec
         assert max_new_tokens >= 1
         sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
                                              self._per_tenant(seed))]
         pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
                                                      self._per_tenant(frequency_penalty), self._per_tenant(logit_bias))]
+        cons = [self._constraint_arg(c) for c in self._per_tenant(constraint)]
         for p_ in prompts:
             self._check_tokens(p_)
         if bool(self.active_flags.any()):
             raise RuntimeError("a tenant is still generating")
         stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
+        for t in range(self.T):
+            self._check_constraint(cons[t], stops[t])
         ids, am = dec.prepare(prompts)
         L = ids.shape[1]
         if L > self.Lc:
@@ -1542,9 +1643,10 @@ class TenantSession:
         logits = dec.prefill(ids, am, self.cache)
         for t in range(self.T):
             self._context(t, prompts[t], pps[t])
+            self._write_constraint(t, cons[t], stops[t])
         first = self._first_tokens(logits, sps, L)
         for t in range(self.T):
-            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t)
+            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t])
             self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
@@ -1557,6 +1659,8 @@ class TenantSession:
         raw = logits                                  # (step_logprobs keeps reading the model's own row)
         if self.penalties:                            # counts the token fed in, writes the row the step end chooses from
             logits = ops.step_penalize(raw, self.plogits, self.hist, self.tok, self.active_flags, self.pen, self.bias_id, self.bias_val)
+        if self.constraints:                          # masks the (penalised) row by each tenant's automaton state; the state itself moves below
+            logits = ops.step_constrain(logits, self.clogits, self.c_state, self.c_off, self.c_tok, self.c_acc, self.stop_ids, self.active_flags)
         if self.sampling:
             ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
                                 self.temperature, self.top_k, self.top_p, self.seed)
@@ -1564,6 +1668,9 @@ class TenantSession:
             ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
         if self.logprobs is not None:
             ops.step_logprobs(raw, self.tok, self.n, self.lp_n, self.lp, self.top_id, self.top_lp)
+        if self.constraints:                          # follows the token just chosen; a tenant that reaches a final state retires here (reason 8)
+            ops.step_constrain_advance(self.tok, self.n, self.c_n, self.c_state, self.c_off, self.c_tok, self.c_next, self.c_acc,
+                                       self.active_flags, self.done)
 
     def _state(self):
         st = [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
@@ -1571,16 +1678,18 @@ class TenantSession:
             st = st + [self.lp_n]
         if self.penalties:                            # (the warm-up and the capture step would count their token twice otherwise)
             st = st + [self.hist]
+        if self.constraints:                          # (... and would advance twice)
+            st = st + [self.c_state, self.c_n]
         return st
 
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
         and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
-        one more launch in front of the last) alone."""
+        one more launch in front of the last; constraints: one more in front of the last and one behind it) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
-               self.sampling, self.logprobs, self.penalties)
+               self.sampling, self.logprobs, self.penalties, self.constraints)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:
@@ -1631,7 +1740,9 @@ class TenantSession:
         top-p, whatever the request sampled with -- and the k = session(logprobs=k) most probable tokens of that step with theirs, in descending
         order (include/bitdelta_hip.h, bd_srv_token_logprobs).  In a session(penalties=True) too the entries are computed from the RAW logits of
         the step, not from the penalised row the token was chosen from: a banned token keeps its model probability, and a token forced by a bias
-        is reported with the probability the model gave it.  ValueError in a session made without logprobs."""
+        is reported with the probability the model gave it.  The same holds in a session(constraints=True): the entries describe the RAW row,
+        not the masked one, so a token the automaton forbids appears in the lists with its model probability and the chosen token is reported
+        with the probability the model gave it, not renormalised over the allowed set.  ValueError in a session made without logprobs."""
         if self.logprobs is None:
             raise ValueError("this session keeps no log-probabilities: make it with session(logprobs=k), 0 <= k <= %d" % ops.LOGPROBS_MAX)
         n = min(int(self.n[t]), self.out.shape[1])

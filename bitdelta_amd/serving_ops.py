@@ -427,6 +427,98 @@ def step_penalize(logits, out, hist, tok, active, pen, bias_id=None, bias_val=No
     return out
 
 
+CONSTRAINT_STATES_MAX = 1 << 16      # include/bitdelta_hip.h (BD_CONSTRAINT_STATES_MAX / _EDGES_MAX / _STOP_MAX)
+CONSTRAINT_EDGES_MAX = 1 << 20
+CONSTRAINT_STOP_MAX = 64
+
+
+def _automaton_args(R, state, off, edge_tok, accepting, edge_next=None):
+    """the checks the three constraint launches share on the per-row automaton arrays; returns (S, E, edge_tok pointer, edge_next pointer)"""
+    require_gpu(state, off, accepting)
+    assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() == R
+    assert off.dim() == 2 and off.shape[0] == R and off.dtype == torch.int32 and off.is_contiguous()
+    S = off.shape[1] - 1
+    assert 1 <= S <= CONSTRAINT_STATES_MAX
+    assert accepting.shape == (R, S) and accepting.dtype in (torch.bool, torch.uint8) and accepting.is_contiguous()
+    assert edge_tok.dim() == 2 and edge_tok.shape[0] == R and edge_tok.dtype == torch.int32 and edge_tok.is_contiguous()
+    E = edge_tok.shape[1]
+    assert E <= CONSTRAINT_EDGES_MAX
+    if edge_next is not None:
+        assert edge_next.shape == (R, E) and edge_next.dtype == torch.int32 and edge_next.is_contiguous()
+    if E == 0:
+        return S, 0, None, None
+    require_gpu(edge_tok, *([] if edge_next is None else [edge_next]))
+    return S, E, ptr(edge_tok), None if edge_next is None else ptr(edge_next)
+
+
+def _constrain_args(logits, out, state, off, edge_tok, accepting, stop_ids):
+    """the checks constrain_rows and step_constrain share; returns (out, S, E, edge_tok pointer, ns, stop_ids pointer)"""
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and logits.dtype in (torch.float16, torch.bfloat16)
+    if out is None:
+        out = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
+    require_gpu(out)
+    assert out.shape == (R, V) and out.dtype == logits.dtype and out.stride(1) == 1
+    S, E, et, _ = _automaton_args(R, state, off, edge_tok, accepting)
+    if stop_ids is None or stop_ids.shape[1] == 0:
+        return out, S, E, et, 0, None
+    require_gpu(stop_ids)
+    ns = stop_ids.shape[1]
+    assert stop_ids.shape == (R, ns) and ns <= CONSTRAINT_STOP_MAX and stop_ids.dtype == torch.long and stop_ids.is_contiguous()
+    return out, S, E, et, ns, ptr(stop_ids)
+
+
+def constrain_rows(logits, state, off, edge_tok, accepting, stop_ids=None, out=None):
+    """The constrained copy of logits [R, V] (16-bit, V % 8 == 0): every element whose token the row's automaton state does not allow is -inf,
+    every other element keeps its bits; include/bitdelta_hip.h (bd_srv_constrain_rows) is the definition.  state int32 [R] (negative: no
+    constraint, the row is copied); per row, in CSR form, off int32 [R, S + 1], edge_tok int32 [R, E] (sorted within a state), accepting
+    bytes [R, S]; stop_ids long [R, ns <= 64] (-1: an empty slot; None: no list), allowed in an accepting state.  Rows may be strided
+    (stride % 8 == 0, 16-byte aligned; logits of another layout are copied first, as in penalize_rows); out: a tensor of the logits' shape and
+    dtype to write into instead of a new one."""
+    require_gpu(logits)
+    assert logits.dim() == 2
+    R, V = logits.shape
+    sl = logits.stride(0) if R > 1 else V
+    if logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16:             # (token_logprobs' rule: such rows are copied first)
+        logits, sl = logits.contiguous(), V
+    out, S, E, et, ns, sp = _constrain_args(logits, out, state, off, edge_tok, accepting, stop_ids)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_constrain_rows(ptr(logits), sl, V, ptr(out), out.stride(0) if R > 1 else V, ptr(state), ptr(off), et, ptr(accepting),
+                                          S, E, sp, ns, R, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_constrain_rows")
+    return out
+
+
+def step_constrain(logits, out, state, off, edge_tok, accepting, stop_ids, active):
+    """constrain_rows inside a ragged decode step, logits [T, V] -> out [T, V], between the lm_head (or step_penalize) and the step end, which
+    then reads `out`.  An inactive tenant's row of out is not touched.  The launch only reads state; step_constrain_advance moves it.  active
+    [T] bool / uint8."""
+    require_gpu(logits, active)
+    out, S, E, et, ns, sp = _constrain_args(logits, out, state, off, edge_tok, accepting, stop_ids)
+    T, V = logits.shape
+    assert active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == T
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_constrain(ptr(logits), logits.stride(0), V, ptr(out), out.stride(0), ptr(state), ptr(off), et, ptr(accepting), S, E,
+                                          sp, ns, ptr(active), T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_constrain")
+    return out
+
+
+def step_constrain_advance(tok, n, c_n, state, off, edge_tok, edge_next, accepting, active, done):
+    """The automaton's transition behind the step end: for every tenant whose token count n[t] moved past the launch's own counter c_n[t]
+    (which then follows it), state[t] follows the edge on tok[t] when its state has one; a tenant that reaches a final state (accepting, no
+    edges) while still active is retired: active[t] = 0, done[t] |= 8.  include/bitdelta_hip.h (bd_srv_step_constrain_advance) is the
+    definition.  tok [T] or [T, 1], n, c_n long; state int32 [T]; edge_next int32 [T, E]; active, done [T] bool / uint8."""
+    require_gpu(tok, n, c_n, active, done)
+    T = state.numel()
+    S, E, et, en = _automaton_args(T, state, off, edge_tok, accepting, edge_next)
+    for x in (tok, n, c_n):
+        assert x.dtype == torch.long and x.is_contiguous() and x.numel() == T
+    for x in (active, done):
+        assert x.dtype in (torch.bool, torch.uint8) and x.is_contiguous() and x.numel() == T
+    with torch.cuda.device(state.device):
+        check(lib().bd_srv_step_constrain_advance(ptr(tok), ptr(n), ptr(c_n), ptr(state), ptr(off), et, en, ptr(accepting), S, E, ptr(active),
+                                                  ptr(done), T, stream_ptr()), "srv_step_constrain_advance")
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

@@ -420,6 +420,62 @@ int bd_srv_penalize_rows(const void* logits, int64_t sl, int V, void* out, int64
 int bd_srv_step_penalize(const void* logits, int64_t sl, int V, void* out, int64_t so, int16_t* hist, int64_t sh, const int64_t* tok,
                          const uint8_t* active, const float* pen, const int32_t* bias_id, const float* bias_val, int nb, int T, int dtype,
                          void* stream);
+/* bd_srv_constrain_rows: a request's output restricted to a deterministic automaton over token ids (vLLM's guided_choice / guided_regex /
+ * allowed_token_ids, OpenAI's structured outputs; a regex or schema compiler outside this library produces the automaton): each row of 16-bit
+ * logits becomes the row with every token its state does not allow set to -inf, which the token choice (argmax, bd_srv_sample_rows, the
+ * step-end launches) then reads in place of the raw or penalised one.  The automaton is per row, in CSR form:
+ *   state[r]     int32: the row's current state, 0 <= state < S; a negative value = no constraint.
+ *   off          int32 [R, S + 1]: the edges of state s of row r are off[r, s] .. off[r, s + 1] - 1.
+ *   edge_tok     int32 [R, E]: the edges' tokens; within a state sorted ascending, no token twice.
+ *   accepting    bytes [R, S]: in an accepting state the request's own stop ids are allowed next to the state's edges.
+ *   stop_ids     int64 [R, ns]: the request's stop ids, -1 = an empty slot.
+ * For every v in [0, V):
+ *   out[v] = l[v], the same 16 bits, when state[r] < 0, or v is an edge token of state[r], or state[r] is accepting and v == stop_ids[r, j] for
+ *            some j (a stop id >= 0);
+ *   out[v] = -inf otherwise.
+ * A kept element keeps its bits: -0, subnormals, NaN and +-inf pass through (no float is made of a logit).  Device values the host could not
+ * have written are neutralised: a state >= S masks nothing (as a negative one), slice bounds are clamped into [0, E] (off[s + 1] < off[s]: an
+ * empty slice), an edge token outside [0, V) matches nothing.  An out element is a pure function of (l[v], v, the state's edge list, the
+ * accepting byte, the stop list): no atomics, nothing depends on R, on the strides, on thread or block order, or on graph or eager execution.
+ * tests/constraint_ref.py restates the definition.
+ * logits / out [R, V] fp16 / bf16 with row strides sl / so (elements); elements V .. stride - 1 of a row are neither read nor written.  The
+ * automaton arrays are contiguous.  edge_tok may be NULL when E == 0, stop_ids when ns == 0.  Checked before any device call, in this order:
+ * R < 0, V < 1, V > 2^22 -> BD_E_BAD_SHAPE; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE; R == 0 -> BD_OK, nothing launched; S outside
+ * 1 .. BD_CONSTRAINT_STATES_MAX, E outside 0 .. BD_CONSTRAINT_EDGES_MAX, ns outside 0 .. BD_CONSTRAINT_STOP_MAX or R > 65535 ->
+ * BD_E_BAD_SHAPE; a needed pointer NULL -> BD_E_NULL; V % 8, a stride % 8 or < V, logits / out not 16-byte, state / off / edge_tok not 4-byte
+ * or stop_ids not 8-byte aligned -> BD_E_BAD_SHAPE.
+ * Several blocks per row: grid (ceil(V / 2048), R), one 16-byte vector of logits per thread; membership is a lower-bound search of the
+ * vector's first index in the state's sorted slice and at most 8 comparisons from there, never a pass over the whole edge list.  No LDS. */
+#define BD_CONSTRAINT_STATES_MAX 65536
+#define BD_CONSTRAINT_EDGES_MAX 1048576
+#define BD_CONSTRAINT_STOP_MAX 64
+int bd_srv_constrain_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* state, const int32_t* off,
+                          const int32_t* edge_tok, const uint8_t* accepting, int S, int E, const int64_t* stop_ids, int ns, int R, int dtype,
+                          void* stream);
+/* bd_srv_step_constrain: bd_srv_constrain_rows inside a ragged decode step, between the lm_head (or bd_srv_step_penalize) and
+ * bd_srv_step_end_ragged / bd_srv_step_end_sample (which then read `out`); active bytes [T].  An inactive tenant's out row is not touched and
+ * nothing of it is read.  The launch only READS state: several blocks share a row, and the state moves in bd_srv_step_constrain_advance, behind
+ * the step end.  Checks as above with T for R; active NULL -> BD_E_NULL. */
+int bd_srv_step_constrain(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* state, const int32_t* off,
+                          const int32_t* edge_tok, const uint8_t* accepting, int S, int E, const int64_t* stop_ids, int ns,
+                          const uint8_t* active, int T, int dtype, void* stream);
+/* bd_srv_step_constrain_advance: the automaton's transition, launched BEHIND the step end (and bd_srv_step_logprobs) with the token the step
+ * chose: one block, one thread per tenant, bd_srv_step_logprobs' counter discipline.  tok / n int64 [T] (the step end's), c_n int64 [T] the
+ * launch's own counter, state int32 [T], off / edge_tok / accepting as above, edge_next int32 [T, E] the edges' target states, active / done
+ * bytes [T] (the step end's).  For every tenant t:
+ *   n[t] == c_n[t]: the tenant emitted nothing in this step; nothing of it is read further or written.
+ *   otherwise c_n[t] = n[t]; with s = state[t] in [0, S) (any other value: nothing more happens) and y = tok[t]:
+ *     y is an edge token of s and that edge's edge_next lies in [0, S): state[t] = edge_next.  Otherwise the state stays -- a stop id in an
+ *     accepting state (the step end has retired the tenant already), or device values the host could not have written: the rule is total.
+ *     The state after that is FINAL when it is accepting and has no edges; then, when active[t] != 0: active[t] = 0 and done[t] |= 8 (the
+ *     constraint is complete; the reasons 1 / 2 / 4 of bd_srv_step_end_ragged keep their meaning).  A tenant the step end has retired in this
+ *     step has its state advanced and its done byte left alone.
+ * Integer work: exact.  Checked before any device call, in this order: T < 0 -> BD_E_BAD_SHAPE; T == 0 -> BD_OK, nothing launched; S or E out of
+ * range (as above) or T > 1024 -> BD_E_BAD_SHAPE; a needed pointer NULL (edge_tok / edge_next only when E > 0) -> BD_E_NULL; tok / n / c_n not
+ * 8-byte, state / off / edge_tok / edge_next not 4-byte aligned -> BD_E_BAD_SHAPE. */
+int bd_srv_step_constrain_advance(const int64_t* tok, const int64_t* n, int64_t* c_n, int32_t* state, const int32_t* off,
+                                  const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* accepting, int S, int E, uint8_t* active,
+                                  uint8_t* done, int T, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
