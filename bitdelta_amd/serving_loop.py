@@ -428,6 +428,9 @@ class TenantDecoder(nn.Module):
         self._capture_stream = None
         self._tenant_views = {}         # tenant -> one-tenant view of this decoder (tenant_view)
         self._sessions = weakref.WeakSet()   # live TenantSessions: load_tenant drops their captured graphs when a hand-off scale changes
+        # one tag per slot: WHICH fine-tune it holds, as far as anybody can tell.  A fresh unique object at construction and at every load_tenant;
+        # load_tenant(tag=) names it instead (tenant_tag).
+        self._tags = [object() for _ in range(tenants)]
         self.fuse_qkv_norm = False      # RMSNorm folded into the q|k|v launch
         # RMSNorm folded into the gate|up launch (SwiGLU stays in its epilogue either way): every block re-normalises all rows (rows + norm
         # weights from L2) to save one ~4.5 us launch.  Same-process A/Bs at the end of round 4, with the resident-row form (which needs no
@@ -617,8 +620,14 @@ class TenantDecoder(nn.Module):
         setattr(layer, "_hn_" + which, ((nw.float() / s).to(nw.dtype), s))
         return True
 
+    def tenant_tag(self, t):
+        """Slot t's fine-tune tag: the hashable load_tenant(tag=) gave it, or the unique object it got at construction / at its last untagged load.
+        Two slots -- or one slot at two times -- hold the same fine-tune, as far as the decoder can tell, exactly when their tags are equal.
+        Nothing in this package reads the tag yet: it is bookkeeping for a caller that keeps data per fine-tune outside the decoder."""
+        return self._tags[t]
+
     @torch.no_grad()
-    def load_tenant(self, t, state):
+    def load_tenant(self, t, state, tag=None):
         """Replace the fine-tune in slot t IN PLACE (state: see tenant_state): every delta Linear's sign words and scales through
         FusedDeltaLinear.load_tenant, the tenant's rows of the norms, the embedding and the lm_head by copies on the current stream.  Storage and
         pointers stay, so captured decode steps stay valid and the other tenants' rows are not touched.  The one thing a captured step bakes that
@@ -627,12 +636,20 @@ class TenantDecoder(nn.Module):
         sessions is dropped (the next step captures again).  Host synchronisation: at most ONE device-to-host read per load -- the maxima of
         the new norm rows of every cached entry, reduced on the device and read back together (_hn_peaks); none when no hand-off norm is cached
         yet, or when the state's norm rows are host tensors.  That read waits for work already queued on the stream.  Refuses a decoder whose per-tenant tensors are one row expanded (shared_heads).
-        The caller makes sure slot t is not generating (TenantSession.load_tenant checks)."""
+        The caller makes sure slot t is not generating (TenantSession.load_tenant checks).
+        tag: the slot's fine-tune tag afterwards (tenant_tag).  None, the default, gives it a fresh unique object: nothing kept from before the
+        load matches it.  A hashable (say the fine-tune's name) is the CALLER's statement that equal tags mean equal weights: after A -> B -> A in
+        one slot the tag is A's again, and every slot loaded with tag A compares equal.  An unhashable tag is refused (TypeError) first, and
+        every refusal leaves the tag as it was.  From the first write on the slot carries a fresh unique object, and the caller's tag is
+        assigned after the last: a load that fails midway never leaves a tag that matches anything on partly new weights."""
+        if tag is not None:
+            hash(tag)
         self._check_state(t, state)
         require_gpu(self.embed)
         assert not torch.cuda.is_current_stream_capturing(), "a load reads the hand-off scale on the host: not inside a graph capture"
         peaks = self._hn_peaks(t, state)                   # the load's one host read (none without a cached hand-off norm)
         rescaled = False
+        self._tags[t] = object()                           # (every refusal is behind us; the first write follows)
         for li, (layer, d) in enumerate(zip(self.layers, state["layers"])):
             for name in self._LINEARS:
                 getattr(layer, name).load_tenant(t, *d[name])
@@ -645,6 +662,8 @@ class TenantDecoder(nn.Module):
         # The decoder's own one-tenant view is dropped and rebuilt on its next use.  That is enough: a view slices this storage and caches nothing
         # derived from tenant data (it only prefills, where no hand-off norm is made), so a view a caller still holds reads the new fine-tune too.
         self._tenant_views.pop(t, None)
+        if tag is not None:
+            self._tags[t] = tag
         if rescaled:
             for slot in self._static.values():
                 slot["graph"] = None
@@ -1353,16 +1372,19 @@ class TenantSession:
 
     # ------------------------------------------------------------ admission
     @torch.no_grad()
-    def load_tenant(self, t, state):
+    def load_tenant(self, t, state, tag=None):
         """Put another fine-tune into slot t (TenantDecoder.load_tenant) while the other tenants keep generating: refused (RuntimeError) while
         tenant t is active.  Runs on the current stream, i.e. ordered between the replays around it; tenant t's validity bytes, stop reason, token
         count and output row are cleared, nobody else's state, cache rows or validity bytes are touched.  Host reads: tenant t's own activity
-        flag (as in submit) and, where a hand-off norm is cached, the decoder's one read of the new norm rows' maxima."""
+        flag (as in submit) and, where a hand-off norm is cached, the decoder's one read of the new norm rows' maxima.
+        tag: the slot's fine-tune tag afterwards (TenantDecoder.load_tenant, tenant_tag); a refused load leaves the tag as it was."""
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
+        if tag is not None:
+            hash(tag)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
-        rescaled = self.dec.load_tenant(t, state)
+        rescaled = self.dec.load_tenant(t, state, tag=tag)
         self._kv_start[t] = None                      # the cache rows belong to the fine-tune that left: nothing to extend
         self.cache["valid"][t].zero_()
         self.done[t] = 0
