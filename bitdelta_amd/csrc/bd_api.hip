@@ -27,6 +27,7 @@
 #include "bd_logprobs.h"
 #include "bd_penalize.h"
 #include "bd_constrain.h"
+#include "bd_stop_seq.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2294,5 +2295,22 @@ extern "C" int bd_srv_step_constrain_advance(const int64_t* tok, const int64_t* 
     hipLaunchKernelGGL((constrain_advance_kernel<CON_ADVANCE_T_MAX>), dim3(1), dim3((unsigned)((T + 63) / 64 * 64)), 0, (hipStream_t)stream, (const long long*)tok,
                        (const long long*)n, (long long*)c_n, (int*)state, (const int*)off, (const int*)edge_tok, (const int*)edge_next,
                        (const unsigned char*)accepting, S, E, (unsigned char*)active, (unsigned char*)done, T);
+    return launch_status();
+}
+
+// (behind every kernel that existed before it: see the note above bd_srv_prefill_attention_cached)
+extern "C" int bd_srv_step_stop_sequences(const int64_t* out, int64_t s_out, int out_cap, const int64_t* n, int64_t* ss_n, const int32_t* seq_tok,
+                                          const int32_t* seq_len, int Q, int W, int32_t* hit, int32_t* hold, uint8_t* active, uint8_t* done, int T,
+                                          void* stream) {
+    if (T < 0 || T > SS_T_MAX || Q < 1 || Q > SS_Q_MAX || W < 1 || W > SS_W_MAX || out_cap < 0 || s_out < out_cap) return BD_E_BAD_SHAPE;
+    if (T == 0) return BD_OK;
+    if (!out || !n || !ss_n || !seq_tok || !seq_len || !hit || !hold || !active || !done) return BD_E_NULL;
+    if (!aligned_to(out, 8) || !aligned_to(n, 8) || !aligned_to(ss_n, 8) || !aligned_to(seq_tok, 4) || !aligned_to(seq_len, 4) ||
+        !aligned_to(hit, 4) || !aligned_to(hold, 4))
+        return BD_E_BAD_SHAPE;
+    // one thread per (sequence, length) pair at a pitch of SS_W_MAX lengths per sequence, whole waves
+    hipLaunchKernelGGL((stop_sequences_kernel<SS_Q_MAX, SS_W_MAX>), dim3((unsigned)T), dim3((unsigned)((Q * SS_W_MAX + 63) / 64 * 64)), 0,
+                       (hipStream_t)stream, (const long long*)out, (long long)s_out, out_cap, (const long long*)n, (long long*)ss_n,
+                       (const int*)seq_tok, (const int*)seq_len, Q, W, (int*)hit, (int*)hold, (unsigned char*)active, (unsigned char*)done);
     return launch_status();
 }

@@ -1076,7 +1076,7 @@ class TenantDecoder(nn.Module):
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
     def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
-                max_constraint_states=256, max_constraint_edges=4096):
+                max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
         request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
         logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
@@ -1086,9 +1086,14 @@ class TenantDecoder(nn.Module):
         allocates nothing for them and runs the step it ran before.
         constraints=True: every request may also carry constraint= a TokenAutomaton (constraint.py) of at most max_constraint_states states and
         max_constraint_edges edges, which restricts what the request may emit; independent of the other three.  The default session refuses
-        one, allocates nothing for it and runs the step it ran before."""
+        one, allocates nothing for it and runs the step it ran before.
+        stop_sequences=True: every request may also carry stop_sequences= a list of token-id lists (at most max_stop_sequences <= 16 of at most
+        max_stop_sequence_len <= 32 ids each) and retires, with reason 16, in the step that completes one of them (TenantSession.stop_match,
+        streamable); independent of the other four.  The default session refuses them, allocates nothing for them and runs the step it ran
+        before."""
         return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias,
-                             constraints=constraints, max_constraint_states=max_constraint_states, max_constraint_edges=max_constraint_edges)
+                             constraints=constraints, max_constraint_states=max_constraint_states, max_constraint_edges=max_constraint_edges,
+                             stop_sequences=stop_sequences, max_stop_sequences=max_stop_sequences, max_stop_sequence_len=max_stop_sequence_len)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1252,6 +1257,64 @@ def logprobs_slot(n, lp_n, cap):
     return (j if 0 <= j < cap else None), n
 
 
+def stop_sequence_table(seqs, Q, W, vocab=None):
+    """The stop sequences of one request, validated on the host, as the rows the device table takes: (tok, lens) with tok Q lists of W ints --
+    sequence q in tok[q][:lens[q]], padded with -1 -- and lens Q ints, 0 for an unused slot.  The caller's order is kept: hit is an index into
+    it.  seqs: None or a list / tuple of token-id sequences (lists / tuples), each of 1 .. W integer ids (no bools) in [0, vocab) when the
+    vocabulary size is given, at most Q of them.  Anything else -- an empty sequence, an id that is no integer or lies outside the vocabulary,
+    too many sequences, a sequence that is too long -- raises ValueError."""
+    if seqs is None:
+        seqs = ()
+    if not isinstance(seqs, (list, tuple)):
+        raise ValueError("stop_sequences = %r: a list of token-id lists is required" % (seqs,))
+    if len(seqs) > Q:
+        raise ValueError("%d stop sequences: at most %d are kept per request" % (len(seqs), Q))
+    tok, lens = [], []
+    for s_ in seqs:
+        if not isinstance(s_, (list, tuple)):
+            raise ValueError("stop sequence %r: a list of token ids is required" % (s_,))
+        if len(s_) == 0:
+            raise ValueError("an empty stop sequence")
+        if len(s_) > W:
+            raise ValueError("a stop sequence of %d tokens: at most %d are kept" % (len(s_), W))
+        row = []
+        for i in s_:
+            try:
+                if isinstance(i, bool):
+                    raise TypeError
+                i = operator.index(i)
+            except TypeError:
+                raise ValueError("stop sequence %r: integer token ids are required" % (s_,))
+            if i < 0 or i > 2 ** 31 - 1 or (vocab is not None and i >= vocab):
+                raise ValueError("stop sequence %r: token id %d is outside the vocabulary" % (s_, i))
+            row.append(i)
+        tok.append(row + [-1] * (W - len(row)))
+        lens.append(len(row))
+    pad = Q - len(tok)
+    return tok + [[-1] * W for _ in range(pad)], lens + [0] * pad
+
+
+def stop_sequence_scan(tokens, seqs):
+    """include/bitdelta_hip.h's rule (bd_srv_step_stop_sequences) for one tenant on host integers: tokens = this turn's tokens so far (the prompt
+    and earlier turns never take part), seqs = the request's sequences in the caller's order.  Returns (hit, hold): the lowest index of a
+    sequence the tokens END with, or -1; and the largest k such that the last k tokens are the first k of a sequence longer than k -- the
+    trailing tokens a streaming caller must not show yet -- which is 0 on a hit.  Admission uses it for the first token, which comes from the
+    prefill and not from a step."""
+    y, n = list(tokens), len(tokens)
+    for q, s_ in enumerate(seqs):
+        s_ = list(s_)
+        if 1 <= len(s_) <= n and y[n - len(s_):] == s_:
+            return q, 0
+    hold = 0
+    for s_ in seqs:
+        s_ = list(s_)
+        for k in range(min(len(s_) - 1, n), hold, -1):
+            if y[n - k:] == s_[:k]:
+                hold = k
+                break
+    return -1, hold
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -1294,16 +1357,38 @@ class TenantSession:
     Nothing is baked into the captured graph.  result_logprobs keeps reporting the RAW logits' distribution.  Without constraints=True the
     session refuses a constraint (ValueError), allocates none of this and launches nothing more.
 
+    stop_sequences=True: a request may carry stop_sequences= a list of token-id lists (stop_sequence_table; include/bitdelta_hip.h,
+    bd_srv_step_stop_sequences, defines a match) -- OpenAI's `stop`, on token ids: the project has no tokenizer, so the caller turns a stop string
+    into the one or several token sequences that spell it and passes them all.  The session keeps, per tenant, the table at fixed sizes (ss_tok
+    [T, Q, W] int32, ss_len [T, Q]; Q = max_stop_sequences, W = max_stop_sequence_len), the launch's own counter (ss_n [T]) and its two results
+    (hit [T] int32: the index of the matched sequence or -1; hold [T]: how many trailing tokens are a proper prefix of a sequence) as device
+    arrays written at admission, and ONE more launch ends the step (serving_ops.step_stop_sequences, behind the step end, step_logprobs and
+    step_constrain_advance): a tenant whose turn now ends with one of its sequences retires in that very step with reason 16 -- OR-ed to the
+    reasons 1 / 2 / 4 when the step end retired it on the same token.  Only this turn's tokens are compared: a sequence that straddles the
+    prompt (or an earlier turn) and the output does not match.  The matched tokens stay in result(t), as a stop token does; stop_match(t) says
+    which sequence matched and how long it is, streamable(t) how many leading tokens of result(t) are safe to show (n - hold).  The first
+    token comes from the prefill, so admission applies the same rule on the host (stop_sequence_scan): a one-token sequence equal to it
+    retires the tenant at admission.  extend matches the new turn only.  A constraint and stop sequences are independent: the automaton is
+    not taught to allow the sequences, and a sequence it never lets through never matches -- the two are the caller's to keep consistent.
+    Nothing is baked into the captured graph.  Without stop_sequences=True the session refuses them (ValueError), allocates none of this and
+    launches nothing more.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full, 8 = the constraint is complete (a final state
-    of the request's automaton was reached); 0 = still active or never submitted."""
+    of the request's automaton was reached), 16 = the turn ends with one of the request's stop sequences; 0 = still active or never submitted."""
 
     def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
-                 max_constraint_states=256, max_constraint_edges=4096):
+                 max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8):
         self.logprobs = logprobs_count(logprobs)
         self.penalties = bool(penalties)
         self.constraints = bool(constraints)
+        self.stop_sequences = bool(stop_sequences)
+        if self.stop_sequences:
+            for v, what, top in ((max_stop_sequences, "max_stop_sequences", ops.STOP_SEQ_MAX),
+                                 (max_stop_sequence_len, "max_stop_sequence_len", ops.STOP_SEQ_LEN_MAX)):
+                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
+                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
         if self.constraints:
             for v, what, top in ((max_constraint_states, "max_constraint_states", ops.CONSTRAINT_STATES_MAX),
                                  (max_constraint_edges, "max_constraint_edges", ops.CONSTRAINT_EDGES_MAX)):
@@ -1365,6 +1450,13 @@ class TenantSession:
             self.c_next = torch.zeros(T, E, dtype=torch.int32, device=dev)
             self.c_acc = torch.zeros(T, S, dtype=torch.uint8, device=dev)
             self.clogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+        if self.stop_sequences:                       # per tenant: the table at the session's sizes, the launch's counter, its two results
+            Q, W = max_stop_sequences, max_stop_sequence_len
+            self.ss_tok = torch.full((T, Q, W), -1, dtype=torch.int32, device=dev)
+            self.ss_len = torch.zeros(T, Q, dtype=torch.int32, device=dev)
+            self.ss_n = torch.zeros(T, dtype=torch.long, device=dev)          # step_stop_sequences' own counter: follows n
+            self.hit = torch.full((T,), -1, dtype=torch.int32, device=dev)
+            self.hold = torch.zeros(T, dtype=torch.int32, device=dev)
         self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
@@ -1400,6 +1492,8 @@ class TenantSession:
         if self.constraints:
             self.c_state[t] = -1
             self.c_n[t] = 0
+        if self.stop_sequences:
+            self._write_stop_sequences(t, self._stop_sequences_arg(()), -1, 0, 0)
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -1427,6 +1521,41 @@ class TenantSession:
         if not isinstance(constraint, TokenAutomaton):
             raise ValueError("constraint = %r: None or a TokenAutomaton is required" % (constraint,))
         return constraint
+
+    def _stop_sequences_arg(self, seqs):
+        """a request's stop_sequences= argument, validated before anything is touched: None for a session made without stop_sequences=True (which
+        takes an empty value only), otherwise (seqs as lists of ints, in the caller's order; stop_sequence_table's rows)"""
+        if not self.stop_sequences:
+            if seqs is None or (isinstance(seqs, (list, tuple)) and len(seqs) == 0):
+                return None
+            raise ValueError("this session takes no stop sequences: make it with session(stop_sequences=True) to pass stop_sequences=")
+        Q, W = self.ss_tok.shape[1], self.ss_tok.shape[2]
+        tok, lens = stop_sequence_table(seqs, Q, W, self.dec.lm_head.shape[-2])
+        return [row[:l] for row, l in zip(tok, lens) if l], (tok, lens)
+
+    def _per_tenant_stop_sequences(self, v):
+        """submit_all's stop_sequences=: one list of token-id lists for all tenants, or a list with one such list per tenant.  The two are told
+        apart by depth: the value is PER TENANT when it is not empty and none of its elements holds a token id directly -- every element is
+        itself a (possibly empty) list / tuple of lists / tuples, e.g. [[[5, 6]], [], [[7], [8, 9]], []] -- and must then have one element per
+        tenant (_per_tenant's rule: ValueError otherwise).  [[5, 6], [7]] is one list of two sequences for all, [] / None is none for all, and
+        [[], []] reads as two tenants without sequences (an empty sequence is never valid, so nothing is lost)."""
+        seq = (list, tuple)
+        if isinstance(v, seq) and len(v) and all(isinstance(e, seq) and all(isinstance(x, seq) for x in e) for e in v):
+            if len(v) != self.T:
+                raise ValueError("%d values for %d tenants" % (len(v), self.T))
+            return list(v)
+        return [v] * self.T
+
+    def _write_stop_sequences(self, t, ss, hit, hold, n):
+        """a stop-sequence session: tenant t's table rows (_stop_sequences_arg's), results and counter.  Torch ops on the current stream, no host
+        read."""
+        dev = self.dec.dev
+        tok, lens = ss[1]
+        self.ss_tok[t] = torch.tensor(tok, dtype=torch.int32).to(dev)
+        self.ss_len[t] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        self.hit[t] = hit
+        self.hold[t] = hold
+        self.ss_n[t] = n
 
     def _check_constraint(self, con, stops):
         """the checks that need the session's sizes and the request's stop ids (TokenAutomaton.check), before anything is touched"""
@@ -1536,9 +1665,10 @@ class TenantSession:
             raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
         return s_
 
-    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0, con=None):
+    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0, con=None, ss=None):
         """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw); row: its row of that prefill;
-        con: the request's automaton, advanced here once, on the host, with that first token"""
+        con: the request's automaton, advanced here once, on the host, with that first token; ss: _stop_sequences_arg's value, matched here
+        once, on the host, against that first token"""
         if self.sampling:
             self._write_params(t, sp)
         if self.logprobs is not None:                 # the turn's entries restart with it, as result() does
@@ -1554,6 +1684,10 @@ class TenantSession:
                 s_ = con.step(0, first)
                 self.c_state[t] = s_
                 reason |= 8 if con.is_final(s_) else 0
+        if self.stop_sequences:                       # the rule of the launch for n = 1: a one-token sequence equal to the first token is a hit
+            hit, hold = stop_sequence_scan([first], ss[0])
+            self._write_stop_sequences(t, ss, hit, hold, 1)
+            reason |= 16 if hit >= 0 else 0
         self.stop_ids[t].fill_(-1)
         if stops:
             self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long, device=self.dec.dev)
@@ -1568,19 +1702,22 @@ class TenantSession:
 
     @torch.no_grad()
     def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
         alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
         session(sampling=True); the first token's draw index is the padded length L.  repetition_penalty / presence_penalty /
         frequency_penalty / logit_bias: penalty_params, in a session(penalties=True); the context of the turn is the prompt's real tokens.
         constraint: None or a TokenAutomaton, in a session(constraints=True): every token of the turn follows it from its start state; refused
-        (ValueError, before anything is touched) when it does not fit the session's sizes or the vocabulary (TokenAutomaton.check)."""
+        (ValueError, before anything is touched) when it does not fit the session's sizes or the vocabulary (TokenAutomaton.check).
+        stop_sequences: a list of token-id lists, in a session(stop_sequences=True): the tenant retires with reason 16 in the step after which
+        this turn's tokens end with one of them (stop_sequence_table's refusals: ValueError, before anything is touched)."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
         sp = self._params(temperature, top_k, top_p, seed)
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         con = self._constraint_arg(constraint)
+        ss = self._stop_sequences_arg(stop_sequences)
         self._check_tokens(prompt)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
@@ -1598,12 +1735,12 @@ class TenantSession:
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
         self._context(t, prompt, pp)
         self._write_constraint(t, con, stops)
-        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con)
+        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con, ss=ss)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
     def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -1617,7 +1754,10 @@ class TenantSession:
         without the session knowing.  temperature / top_k / top_p / seed as in submit (this turn's own; invalid ones raise ValueError before
         anything is touched); the first token's draw index is P + n.  The penalty arguments as in submit (this turn's own); the turn's context is
         everything the conversation held before it plus [last emitted token] + tokens, and its counts start at zero (fold_history).
-        constraint as in submit: it constrains THIS turn's tokens only, from its start state; None leaves the turn free."""
+        constraint as in submit: it constrains THIS turn's tokens only, from its start state; None leaves the turn free.
+        stop_sequences as in submit: they replace the turn before's, and matching restarts with the turn, as result() does -- tokens of earlier
+        turns never take part.  A tenant retired by reason 16 is extended like one retired by a stop token: its last token, the one that
+        completed the sequence, is the one not yet in the cache."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
@@ -1627,6 +1767,7 @@ class TenantSession:
         sp = self._params(temperature, top_k, top_p, seed)
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         con = self._check_constraint(self._constraint_arg(constraint), stops)
+        ss = self._stop_sequences_arg(stop_sequences)
         self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
@@ -1635,15 +1776,16 @@ class TenantSession:
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
         self._context(t, [last] + tokens, pp, fold=True)
         self._write_constraint(t, con, stops)
-        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con)
+        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con, ss=ss)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None):
+                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
         common padded length.  temperature / top_k / top_p / seed and the four penalty arguments: each one value for all (a logit_bias mapping
         is one value) or a list with one value per tenant.  constraint: None or one TokenAutomaton for all, or a list with one (or None) per
-        tenant."""
+        tenant.  stop_sequences: one list of token-id lists for all, or a list with one such list per tenant; the two are told apart by depth
+        (_per_tenant_stop_sequences)."""
         dec = self.dec
         assert max_new_tokens >= 1
         sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
@@ -1651,6 +1793,7 @@ class TenantSession:
         pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
                                                      self._per_tenant(frequency_penalty), self._per_tenant(logit_bias))]
         cons = [self._constraint_arg(c) for c in self._per_tenant(constraint)]
+        sss = [self._stop_sequences_arg(v) for v in self._per_tenant_stop_sequences(stop_sequences)]
         for p_ in prompts:
             self._check_tokens(p_)
         if bool(self.active_flags.any()):
@@ -1668,7 +1811,7 @@ class TenantSession:
             self._write_constraint(t, cons[t], stops[t])
         first = self._first_tokens(logits, sps, L)
         for t in range(self.T):
-            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t])
+            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t], ss=sss[t])
             self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
@@ -1693,6 +1836,8 @@ class TenantSession:
         if self.constraints:                          # follows the token just chosen; a tenant that reaches a final state retires here (reason 8)
             ops.step_constrain_advance(self.tok, self.n, self.c_n, self.c_state, self.c_off, self.c_tok, self.c_next, self.c_acc,
                                        self.active_flags, self.done)
+        if self.stop_sequences:                       # LAST: a turn that now ends with one of its sequences retires here (reason 16, OR-ed)
+            ops.step_stop_sequences(self.out, self.n, self.ss_n, self.ss_tok, self.ss_len, self.hit, self.hold, self.active_flags, self.done)
 
     def _state(self):
         st = [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
@@ -1702,16 +1847,21 @@ class TenantSession:
             st = st + [self.hist]
         if self.constraints:                          # (... and would advance twice)
             st = st + [self.c_state, self.c_n]
+        if self.stop_sequences:                       # (... and would leave a hit of the trial steps behind)
+            st = st + [self.ss_n, self.hit, self.hold]
         return st
 
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
         and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
-        one more launch in front of the last; constraints: one more in front of the last and one behind it) alone."""
+        one more launch in front of the last; constraints: one more in front of the last and one behind it; stop sequences: one more at the very end, on a table of the
+        session's two sizes) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
                self.sampling, self.logprobs, self.penalties, self.constraints)
+        if self.stop_sequences:                       # (a session without them keeps the key it had)
+            key = key + (True, self.ss_tok.shape[1], self.ss_tok.shape[2])
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:
@@ -1755,6 +1905,26 @@ class TenantSession:
         """(tokens, reason): tenant t's new tokens so far as a 1-D CPU tensor, and why it stopped (0 while it is active)"""
         n = min(int(self.n[t]), self.out.shape[1])
         return self.out[t, :n].cpu(), int(self.done[t])
+
+    def _need_stop_sequences(self):
+        if not self.stop_sequences:
+            raise ValueError("this session keeps no stop sequences: make it with session(stop_sequences=True)")
+
+    def stop_match(self, t):
+        """(index, length) of the stop sequence tenant t's turn ends with -- the index into the request's stop_sequences, the lowest when several
+        match, and the number of trailing tokens of result(t) that spell it -- or None when none matched (yet).  ValueError in a session made
+        without stop_sequences."""
+        self._need_stop_sequences()
+        q = int(self.hit[t])
+        return None if q < 0 else (q, int(self.ss_len[t, q]))
+
+    def streamable(self, t):
+        """n - hold: how many leading tokens of result(t) are safe to show -- the trailing `hold` tokens are the beginning of one of the
+        request's stop sequences and may yet be completed.  After a hit hold is 0: whether the matched tokens are shown is the caller's choice
+        (stop_match gives their number).  ValueError in a session made without stop_sequences."""
+        self._need_stop_sequences()
+        n, hold = torch.stack([self.n[t], self.hold[t].long()]).tolist()
+        return min(n, self.out.shape[1]) - hold
 
     def result_logprobs(self, t):
         """(token_logprobs [n], top_ids [n, k], top_logprobs [n, k]) as CPU tensors (float32, int32, float32) for the n tokens result(t) returns:

@@ -519,6 +519,37 @@ def step_constrain_advance(tok, n, c_n, state, off, edge_tok, edge_next, accepti
                                                   ptr(done), T, stream_ptr()), "srv_step_constrain_advance")
 
 
+STOP_SEQ_MAX = 16          # include/bitdelta_hip.h (BD_STOP_SEQ_MAX / BD_STOP_SEQ_LEN_MAX): sequences per request, ids per sequence
+STOP_SEQ_LEN_MAX = 32
+
+
+def step_stop_sequences(out, n, ss_n, seq_tok, seq_len, hit, hold, active, done):
+    """The LAST launch of a ragged step, behind the step end, step_logprobs and step_constrain_advance: for every tenant whose token count n[t]
+    moved past the launch's own counter ss_n[t] (which then follows it), hit[t] = the lowest q whose stop sequence seq_tok[t, q, :seq_len[t, q]]
+    ends this turn's tokens out[t, :n[t]] (-1: none) and hold[t] = the longest proper prefix of a sequence those tokens end with (0 on a hit); a
+    hit retires the tenant: active[t] = 0, done[t] |= 16 -- also next to the reason of a tenant the step end retired in this step.
+    include/bitdelta_hip.h (bd_srv_step_stop_sequences) is the definition.  out [T, cap] long, rows may be strided; n, ss_n [T] long; seq_tok
+    int32 [T, Q, W] and seq_len int32 [T, Q], Q <= 16, W <= 32; hit, hold int32 [T]; active, done [T] bool / uint8."""
+    require_gpu(out, n, ss_n, seq_tok, seq_len, hit, hold, active, done)
+    assert seq_tok.dim() == 3 and seq_tok.dtype == torch.int32 and seq_tok.is_contiguous()
+    T, Q, W = seq_tok.shape
+    assert 1 <= Q <= STOP_SEQ_MAX and 1 <= W <= STOP_SEQ_LEN_MAX
+    assert seq_len.shape == (T, Q) and seq_len.dtype == torch.int32 and seq_len.is_contiguous()
+    assert out.dim() == 2 and out.dtype == torch.long and out.shape[0] == T and (out.stride(1) == 1 or out.shape[1] <= 1)
+    cap = out.shape[1]
+    s_out = out.stride(0) if T > 1 else cap
+    assert s_out >= cap
+    for x in (n, ss_n):
+        assert x.dtype == torch.long and x.is_contiguous() and x.numel() == T
+    for x in (hit, hold):
+        assert x.dtype == torch.int32 and x.is_contiguous() and x.numel() == T
+    for x in (active, done):
+        assert x.dtype in (torch.bool, torch.uint8) and x.is_contiguous() and x.numel() == T
+    with torch.cuda.device(out.device):
+        check(lib().bd_srv_step_stop_sequences(ptr(out), s_out, cap, ptr(n), ptr(ss_n), ptr(seq_tok), ptr(seq_len), Q, W, ptr(hit), ptr(hold),
+                                               ptr(active), ptr(done), T, stream_ptr()), "srv_step_stop_sequences")
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

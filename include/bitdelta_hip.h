@@ -476,6 +476,41 @@ int bd_srv_step_constrain(const void* logits, int64_t sl, int V, void* out, int6
 int bd_srv_step_constrain_advance(const int64_t* tok, const int64_t* n, int64_t* c_n, int32_t* state, const int32_t* off,
                                   const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* accepting, int S, int E, uint8_t* active,
                                   uint8_t* done, int T, void* stream);
+/* bd_srv_step_stop_sequences: a request stopped at a token SEQUENCE (OpenAI's `stop`, vLLM's `stop` / `include_stop_str_in_output`), and the
+ * number of trailing tokens a streaming caller must hold back because they may still become one.  Matching is on token ids: the caller turns a
+ * stop string into the one or several token sequences that spell it and passes them all.  Launched LAST in a ragged decode step, behind the step
+ * end, bd_srv_step_logprobs and bd_srv_step_constrain_advance (which sets its reason only on a still-active tenant), one block per tenant,
+ * bd_srv_step_logprobs' counter discipline with the launch's own counter ss_n.
+ *   out      int64 [T, out_cap] with row stride s_out (elements): the step end's output rows; out[t, 0:n] are this turn's tokens.
+ *   n        int64 [T]: the step end's per-tenant token count.          ss_n  int64 [T]: this launch's own counter.
+ *   seq_tok  int32 [T, Q, W]: tenant t's stop sequences, sequence q in seq_tok[t, q, 0:seq_len[t, q]]; the rest of a row is not compared.
+ *   seq_len  int32 [T, Q]: 1 .. W; 0 = an unused slot.
+ *   hit / hold int32 [T]; active / done bytes [T] (the step end's).
+ * A request carries up to Q <= BD_STOP_SEQ_MAX sequences of 1 .. W <= BD_STOP_SEQ_LEN_MAX ids each.  For every tenant t:
+ *   n[t] == ss_n[t]: the tenant emitted nothing in this step; nothing of it is read further or written (a stale hit stays).
+ *   otherwise ss_n[t] = n[t], and with n = n[t], y = out[t, 0:n] and len_q = seq_len[t, q], seq_q = seq_tok[t, q, 0:len_q]:
+ *     The prompt and earlier turns never take part: only y is compared, so a sequence half in the prompt and half generated does not match.
+ *     hit[t]  = the lowest q with 1 <= len_q <= n and y[n - len_q : n] == seq_q; -1 when there is none.
+ *     hold[t] = the largest k such that some q has k < len_q, k <= n and y[n - k : n] == seq_q[0:k]; 0 when there is none, and 0 when
+ *               hit[t] >= 0.  It is the number of trailing tokens that are a proper prefix of a stop sequence: not to be shown yet.
+ *     On a hit: active[t] = 0 and done[t] |= 16.  Unlike reason 8, the bit is also OR-ed into the byte of a tenant the step end has retired
+ *     in this same step (reasons 1 / 2 / 4): a caller who trims the matched tokens needs to know of the match even when max_new_tokens ran
+ *     out on the same token.
+ *     n > out_cap (or n < 0): nothing can be compared -- hit[t] = -1, hold[t] = 0, no element of `out` is addressed.
+ *   The rule is total on any device values: a seq_len outside 0 .. W counts as 0 (unused); a negative table entry matches nothing, and so
+ *   does an element of `out` that is not a non-negative int32.
+ * Integer work: exact, a pure function of (out[t, 0:n], n, the tenant's table), whatever T, the strides, thread order, graph or eager execution.
+ * tests/stop_seq_ref.py restates the definition.
+ * Checked before any device call, in this order: T < 0, T > 65535, Q outside 1 .. BD_STOP_SEQ_MAX, W outside 1 .. BD_STOP_SEQ_LEN_MAX,
+ * out_cap < 0 or s_out < out_cap -> BD_E_BAD_SHAPE; T == 0 -> BD_OK, nothing launched; a pointer NULL -> BD_E_NULL; out / n / ss_n not 8-byte,
+ * seq_tok / seq_len / hit / hold not 4-byte aligned -> BD_E_BAD_SHAPE.
+ * One thread per (sequence, length) pair; the window of the last W tokens, the table row and the lengths are read once and staged in LDS.  No
+ * atomics, no floating point. */
+#define BD_STOP_SEQ_MAX 16
+#define BD_STOP_SEQ_LEN_MAX 32
+int bd_srv_step_stop_sequences(const int64_t* out, int64_t s_out, int out_cap, const int64_t* n, int64_t* ss_n, const int32_t* seq_tok,
+                               const int32_t* seq_len, int Q, int W, int32_t* hit, int32_t* hold, uint8_t* active, uint8_t* done, int T,
+                               void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
