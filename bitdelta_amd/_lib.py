@@ -67,6 +67,9 @@ SIGNATURES = {
     "bd_srv_step_constrain": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _vp]),
     "bd_srv_step_constrain_advance": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _vp]),
     "bd_srv_step_stop_sequences": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp]),
+    "bd_srv_ban_rows": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _ci, _vp, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "bd_srv_step_ban": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _ci, _vp, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci,
+                              _vp]),
     "bd_srv_rope_kv_append": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_rope": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_decode_attention": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),

@@ -28,6 +28,7 @@
 #include "bd_penalize.h"
 #include "bd_constrain.h"
 #include "bd_stop_seq.h"
+#include "bd_ban.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2313,4 +2314,56 @@ extern "C" int bd_srv_step_stop_sequences(const int64_t* out, int64_t s_out, int
                        (hipStream_t)stream, (const long long*)out, (long long)s_out, out_cap, (const long long*)n, (long long*)ss_n,
                        (const int*)seq_tok, (const int*)seq_len, Q, W, (int*)hit, (int*)hold, (unsigned char*)active, (unsigned char*)done);
     return launch_status();
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// One body for the two ban entry points: step == false is bd_srv_ban_rows (R live rows; n may be NULL: no turn tokens yet), true bd_srv_step_ban
+// (T tenants).
+static int ban_launch(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* ctx, int Lc, const int32_t* ctx_len,
+                      const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram, const int32_t* ban_tok,
+                      const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids, int ns, const uint8_t* active, int R,
+                      int dtype, bool step, void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (Q < 1 || Q > BAN_WORDS_MAX || W < 1 || W > BAN_WORD_LEN_MAX || ns < 0 || ns > BAN_STOP_MAX || Lc < 0 || tok_cap < 0 ||
+        s_tok < (int64_t)tok_cap || (int64_t)Lc + (int64_t)tok_cap > 0x7fffffffll || R > 65535)
+        return BD_E_BAD_SHAPE;
+    if (!logits || !out || !ctx_len || !ban_ngram || !ban_tok || !ban_len || !ban_min || (Lc > 0 && !ctx) || (ns > 0 && !stop_ids) ||
+        (step && (!active || !n)) || (n && tok_cap > 0 && !toks))
+        return BD_E_NULL;
+    if (V % 8 || sl % 8 || so % 8 || sl < V || so < V || !aligned16(logits) || !aligned16(out) || !aligned_to(ctx, 4) || !aligned_to(ctx_len, 4) ||
+        !aligned_to(toks, 8) || !aligned_to(n, 8) || !aligned_to(ban_ngram, 4) || !aligned_to(ban_tok, 4) || !aligned_to(ban_len, 4) ||
+        !aligned_to(ban_min, 4) || !aligned_to(stop_ids, 8))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((V + BAN_BLOCK_ELEMS - 1) / BAN_BLOCK_ELEMS), (unsigned)R);
+#define BD_BAN_LAUNCH(DT, STEP)                                                                                                          \
+    hipLaunchKernelGGL((ban_kernel<DT, STEP>), grid, dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,                   \
+                       (unsigned short*)out, (long long)so, (const int*)ctx, Lc, (const int*)ctx_len, (const long long*)toks,             \
+                       (long long)s_tok, tok_cap, (const long long*)n, (const int*)ban_ngram, (const int*)ban_tok, (const int*)ban_len,   \
+                       Q, W, (const int*)ban_min, (const long long*)stop_ids, ns, (const unsigned char*)active)
+    if (dtype == BD_BF16) {
+        if (step) BD_BAN_LAUNCH(DT_BF16, true); else BD_BAN_LAUNCH(DT_BF16, false);
+    } else {
+        if (step) BD_BAN_LAUNCH(DT_F16, true); else BD_BAN_LAUNCH(DT_F16, false);
+    }
+#undef BD_BAN_LAUNCH
+    return launch_status();
+}
+
+extern "C" int bd_srv_ban_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* ctx, int Lc, const int32_t* ctx_len,
+                               const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram,
+                               const int32_t* ban_tok, const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids,
+                               int ns, int R, int dtype, void* stream) {
+    return ban_launch(logits, sl, V, out, so, ctx, Lc, ctx_len, toks, s_tok, tok_cap, n, ban_ngram, ban_tok, ban_len, Q, W, ban_min, stop_ids, ns,
+                      nullptr, R, dtype, false, stream);
+}
+
+extern "C" int bd_srv_step_ban(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* ctx, int Lc, const int32_t* ctx_len,
+                               const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram,
+                               const int32_t* ban_tok, const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids,
+                               int ns, const uint8_t* active, int T, int dtype, void* stream) {
+    return ban_launch(logits, sl, V, out, so, ctx, Lc, ctx_len, toks, s_tok, tok_cap, n, ban_ngram, ban_tok, ban_len, Q, W, ban_min, stop_ids, ns,
+                      active, T, dtype, true, stream);
 }

@@ -1076,7 +1076,8 @@ class TenantDecoder(nn.Module):
         return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
 
     def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
-                max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8):
+                max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8, bans=False, max_bad_words=16,
+                max_bad_word_len=8):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
         request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
         logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
@@ -1090,10 +1091,14 @@ class TenantDecoder(nn.Module):
         stop_sequences=True: every request may also carry stop_sequences= a list of token-id lists (at most max_stop_sequences <= 16 of at most
         max_stop_sequence_len <= 32 ids each) and retires, with reason 16, in the step that completes one of them (TenantSession.stop_match,
         streamable); independent of the other four.  The default session refuses them, allocates nothing for them and runs the step it ran
-        before."""
+        before.
+        bans=True: every request may also carry no_repeat_ngram_size= / bad_words= / min_new_tokens= (ban_params; at most max_bad_words <= 64
+        sequences of at most max_bad_word_len <= 32 ids each): tokens its own history forbids are never chosen; independent of the other
+        five.  The default session refuses them, allocates nothing for them and runs the step it ran before."""
         return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias,
                              constraints=constraints, max_constraint_states=max_constraint_states, max_constraint_edges=max_constraint_edges,
-                             stop_sequences=stop_sequences, max_stop_sequences=max_stop_sequences, max_stop_sequence_len=max_stop_sequence_len)
+                             stop_sequences=stop_sequences, max_stop_sequences=max_stop_sequences, max_stop_sequence_len=max_stop_sequence_len,
+                             bans=bans, max_bad_words=max_bad_words, max_bad_word_len=max_bad_word_len)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1315,6 +1320,65 @@ def stop_sequence_scan(tokens, seqs):
     return -1, hold
 
 
+def ban_params(no_repeat_ngram_size=0, bad_words=(), min_new_tokens=0, *, vocab=None, max_bad_words=ops.BAN_WORDS_MAX,
+               max_bad_word_len=ops.BAN_WORD_LEN_MAX):
+    """The hard bans of one request, validated on the host: (no_repeat_ngram_size, bad_words, min_new_tokens) as (int, tuple of tuples of ints,
+    int) -- the canonical form: two requests that mean the same compare equal.  include/bitdelta_hip.h (bd_srv_ban_rows) defines what they
+    ban.  no_repeat_ngram_size: an integer 0 .. 8 (0 = off; HF's NoRepeatNGramLogitsProcessor); bad_words: None or a list / tuple of token-id
+    sequences (lists / tuples), each of 1 .. max_bad_word_len integer ids in [0, vocab) when the vocabulary size is given, at most
+    max_bad_words of them, kept in the caller's order (HF's bad_words_ids); min_new_tokens: an integer >= 0 (0 = off; HF's
+    MinNewTokensLengthLogitsProcessor; values past 2^31 - 1 mean the same as that).  Anything else -- a bool or a non-integer where an integer is
+    required, a negative size, an empty sequence, an id outside the vocabulary, too many or too long sequences -- raises ValueError.  The
+    defaults ban nothing (NO_BANS)."""
+    def integer(v, what):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            return operator.index(v)
+        except TypeError:
+            raise ValueError("%s = %r: an integer is required" % (what, v))
+    g = integer(no_repeat_ngram_size, "no_repeat_ngram_size")
+    if not (0 <= g <= ops.BAN_NGRAM_MAX):
+        raise ValueError("no_repeat_ngram_size = %r: an integer 0 .. %d is required (0 = off)" % (no_repeat_ngram_size, ops.BAN_NGRAM_MAX))
+    lo = integer(min_new_tokens, "min_new_tokens")
+    if lo < 0:
+        raise ValueError("min_new_tokens = %r: an integer >= 0 is required (0 = off)" % (min_new_tokens,))
+    if bad_words is None:
+        bad_words = ()
+    if not isinstance(bad_words, (list, tuple)):
+        raise ValueError("bad_words = %r: a list of token-id lists is required" % (bad_words,))
+    if len(bad_words) > max_bad_words:
+        raise ValueError("%d bad words: at most %d are kept per request" % (len(bad_words), max_bad_words))
+    words = []
+    for w in bad_words:
+        if not isinstance(w, (list, tuple)):
+            raise ValueError("bad word %r: a list of token ids is required" % (w,))
+        if len(w) == 0:
+            raise ValueError("an empty bad word")
+        if len(w) > max_bad_word_len:
+            raise ValueError("a bad word of %d tokens: at most %d are kept" % (len(w), max_bad_word_len))
+        row = []
+        for i in w:
+            i = integer(i, "bad word %r: token id" % (w,))
+            if i < 0 or i > 2 ** 31 - 1 or (vocab is not None and i >= vocab):
+                raise ValueError("bad word %r: token id %d is outside the vocabulary" % (w, i))
+            row.append(i)
+        words.append(tuple(row))
+    return g, tuple(words), min(lo, 2 ** 31 - 1)
+
+
+NO_BANS = ban_params()
+
+
+def ban_word_table(words, Q, W):
+    """ban_params' bad words as the rows the device table takes: (tok, lens) with tok Q lists of W ints -- word q in tok[q][:lens[q]], padded with
+    -1 -- and lens Q ints, 0 for an unused slot.  ValueError when the words do not fit Q rows of W ids."""
+    if len(words) > Q or any(not 1 <= len(w) <= W for w in words):
+        raise ValueError("the bad words do not fit a table of %d words of %d ids" % (Q, W))
+    pad = Q - len(words)
+    return [list(w) + [-1] * (W - len(w)) for w in words] + [[-1] * W for _ in range(pad)], [len(w) for w in words] + [0] * pad
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -1373,13 +1437,31 @@ class TenantSession:
     Nothing is baked into the captured graph.  Without stop_sequences=True the session refuses them (ValueError), allocates none of this and
     launches nothing more.
 
+    bans=True: a request may carry no_repeat_ngram_size= / bad_words= / min_new_tokens= (ban_params; include/bitdelta_hip.h, bd_srv_ban_rows,
+    defines the banned set) -- Hugging Face's NoRepeatNGramLogitsProcessor, bad_words_ids and MinNewTokensLengthLogitsProcessor, hard bans that
+    depend on what the request has already written.  The session keeps, per tenant, the conversation's real tokens (ctx [T, Lc] int32 with
+    ctx_len [T]; the host keeps the list and extend appends the earlier turn's emitted tokens and the new ones), the n-gram size (ban_ngram
+    [T]), the bad-word table at fixed sizes (ban_tok [T, Q, W] int32, ban_len [T, Q]; Q = max_bad_words, W = max_bad_word_len) and the
+    minimum turn length (ban_min [T]) as device arrays written at admission, and ONE more launch (serving_ops.step_ban) sits between the
+    lm_head -- behind step_penalize and step_constrain, whose row it then reads -- and the step end: it writes blogits [T, V], -inf at every
+    token the tenant's history (ctx, then out[t, :n]) forbids and the same bits elsewhere, which the step end reads.  The order makes a ban
+    win over a positive logit_bias and over a constraint's edge.  The launch keeps no counter: it is a pure function of the row, ctx, out, n
+    and the tables.  The first token is chosen from serving_ops.ban_rows of the (penalised, constrained) prefill logits.  min_new_tokens holds
+    back the request's stop IDS while the turn is shorter: not its stop sequences (reason 16) and not a constraint's final state (reason 8).
+    Below the longest bad word's length the rule deviates from HF on purpose: a bad word's prefix is matched as soon as the history holds it,
+    so a two-token bad word right behind a one-token prompt is banned.  A request whose bans, alone or with a constraint, leave no finite
+    logit is the caller's error, as a -inf bias on every token is.  Nothing is baked into the captured graph.  result_logprobs keeps reporting
+    the RAW logits' distribution.  Without bans=True the session refuses non-default values (ValueError), allocates none of this and launches
+    nothing more.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full, 8 = the constraint is complete (a final state
     of the request's automaton was reached), 16 = the turn ends with one of the request's stop sequences; 0 = still active or never submitted."""
 
     def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
-                 max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8):
+                 max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8,
+                 bans=False, max_bad_words=16, max_bad_word_len=8):
         self.logprobs = logprobs_count(logprobs)
         self.penalties = bool(penalties)
         self.constraints = bool(constraints)
@@ -1389,6 +1471,13 @@ class TenantSession:
                                  (max_stop_sequence_len, "max_stop_sequence_len", ops.STOP_SEQ_LEN_MAX)):
                 if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
                     raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
+        self.bans = bool(bans)
+        if self.bans:
+            for v, what, top in ((max_bad_words, "max_bad_words", ops.BAN_WORDS_MAX), (max_bad_word_len, "max_bad_word_len", ops.BAN_WORD_LEN_MAX)):
+                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
+                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
+            if max(int(max_stop_ids), 1) > ops.BAN_STOP_MAX:
+                raise ValueError("a session with bans holds at most %d stop ids per request" % ops.BAN_STOP_MAX)
         if self.constraints:
             for v, what, top in ((max_constraint_states, "max_constraint_states", ops.CONSTRAINT_STATES_MAX),
                                  (max_constraint_edges, "max_constraint_edges", ops.CONSTRAINT_EDGES_MAX)):
@@ -1457,6 +1546,16 @@ class TenantSession:
             self.ss_n = torch.zeros(T, dtype=torch.long, device=dev)          # step_stop_sequences' own counter: follows n
             self.hit = torch.full((T,), -1, dtype=torch.int32, device=dev)
             self.hold = torch.zeros(T, dtype=torch.int32, device=dev)
+        if self.bans:                                 # per tenant: the conversation's real tokens, the three parameters at the session's sizes, the masked row
+            V, Q, W = dec.lm_head.shape[-2], max_bad_words, max_bad_word_len
+            self.ctx = torch.zeros(T, self.Lc, dtype=torch.int32, device=dev)
+            self.ctx_len = torch.zeros(T, dtype=torch.int32, device=dev)
+            self.ban_ngram = torch.zeros(T, dtype=torch.int32, device=dev)
+            self.ban_tok = torch.full((T, Q, W), -1, dtype=torch.int32, device=dev)
+            self.ban_len = torch.zeros(T, Q, dtype=torch.int32, device=dev)
+            self.ban_min = torch.zeros(T, dtype=torch.int32, device=dev)
+            self.blogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+            self._ctx_tokens = [[] for _ in range(T)]  # the host's copy of ctx[t, :ctx_len[t]]: extend appends to it
         self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
@@ -1494,6 +1593,8 @@ class TenantSession:
             self.c_n[t] = 0
         if self.stop_sequences:
             self._write_stop_sequences(t, self._stop_sequences_arg(()), -1, 0, 0)
+        if self.bans:
+            self._write_bans(t, NO_BANS, [], [])
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -1532,6 +1633,49 @@ class TenantSession:
         Q, W = self.ss_tok.shape[1], self.ss_tok.shape[2]
         tok, lens = stop_sequence_table(seqs, Q, W, self.dec.lm_head.shape[-2])
         return [row[:l] for row, l in zip(tok, lens) if l], (tok, lens)
+
+    def _ban_params(self, no_repeat_ngram_size, bad_words, min_new_tokens):
+        """one request's validated bans, before anything is touched; a session made without bans=True takes the defaults only"""
+        if not self.bans:
+            bp = ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
+            if bp != NO_BANS:
+                raise ValueError("this session takes no bans: make it with session(bans=True) to pass no_repeat_ngram_size / bad_words / "
+                                 "min_new_tokens")
+            return bp
+        return ban_params(no_repeat_ngram_size, bad_words, min_new_tokens, vocab=self.dec.lm_head.shape[-2], max_bad_words=self.ban_tok.shape[1],
+                          max_bad_word_len=self.ban_tok.shape[2])
+
+    def _per_tenant_bad_words(self, v):
+        """submit_all's bad_words=: one list of token-id lists for all tenants, or a list with one such list per tenant, told apart by depth as
+        _per_tenant_stop_sequences tells stop sequences apart"""
+        return self._per_tenant_stop_sequences(v)
+
+    def _check_conversation(self, tokens):
+        """a ban session keeps the conversation's real tokens as int32, at most one per cache row"""
+        if self.bans and not (len(tokens) <= self.Lc and all(-2 ** 31 <= int(i) < 2 ** 31 for i in tokens)):
+            raise ValueError("the conversation does not fit the ban history (%d tokens, int32 ids)" % self.Lc)
+
+    def _write_bans(self, t, bp, tokens, stops):
+        """a ban session, before the first token is chosen: tenant t's conversation so far (`tokens`: ALL its real tokens up to this turn; the
+        host keeps the list), its three parameters, and the stop ids min_new_tokens holds back.  Torch ops on the current stream, no host
+        read."""
+        if not self.bans:
+            return
+        dev = self.dec.dev
+        tokens = [int(i) for i in tokens]
+        self._ctx_tokens[t] = tokens
+        if tokens:
+            self.ctx[t, :len(tokens)] = torch.tensor(tokens, dtype=torch.int32).to(dev)
+        self.ctx_len[t] = len(tokens)
+        g, words, lo = bp
+        tok, lens = ban_word_table(words, self.ban_tok.shape[1], self.ban_tok.shape[2])
+        self.ban_ngram[t] = g
+        self.ban_tok[t] = torch.tensor(tok, dtype=torch.int32).to(dev)
+        self.ban_len[t] = torch.tensor(lens, dtype=torch.int32).to(dev)
+        self.ban_min[t] = lo
+        self.stop_ids[t].fill_(-1)                    # (_admit writes the same values again)
+        if stops:
+            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long).to(dev)
 
     def _per_tenant_stop_sequences(self, v):
         """submit_all's stop_sequences=: one list of token-id lists for all tenants, or a list with one such list per tenant.  The two are told
@@ -1638,6 +1782,10 @@ class TenantSession:
         if self.constraints:
             logits = ops.constrain_rows(logits, self.c_state[rows].contiguous(), self.c_off[rows].contiguous(), self.c_tok[rows].contiguous(),
                                         self.c_acc[rows].contiguous(), self.stop_ids[rows].contiguous())
+        if self.bans:                                 # n absent: the turn has no token yet, so min_new_tokens > 0 holds back the stop ids here too
+            logits = ops.ban_rows(logits, self.ctx[rows].contiguous(), self.ctx_len[rows].contiguous(), self.ban_ngram[rows].contiguous(),
+                                  self.ban_tok[rows].contiguous(), self.ban_len[rows].contiguous(), self.ban_min[rows].contiguous(),
+                                  self.stop_ids[rows].contiguous())
         if not self.sampling:
             tok = torch.argmax(logits, dim=-1)
             self._keep_first_logprobs(raw, tok)
@@ -1702,7 +1850,8 @@ class TenantSession:
 
     @torch.no_grad()
     def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
+               bad_words=(), min_new_tokens=0):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
         alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
@@ -1711,14 +1860,18 @@ class TenantSession:
         constraint: None or a TokenAutomaton, in a session(constraints=True): every token of the turn follows it from its start state; refused
         (ValueError, before anything is touched) when it does not fit the session's sizes or the vocabulary (TokenAutomaton.check).
         stop_sequences: a list of token-id lists, in a session(stop_sequences=True): the tenant retires with reason 16 in the step after which
-        this turn's tokens end with one of them (stop_sequence_table's refusals: ValueError, before anything is touched)."""
+        this turn's tokens end with one of them (stop_sequence_table's refusals: ValueError, before anything is touched).
+        no_repeat_ngram_size / bad_words / min_new_tokens: ban_params, in a session(bans=True); the history they look at is the prompt's real
+        tokens followed by the turn's own, and the first token obeys them too."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
         sp = self._params(temperature, top_k, top_p, seed)
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         con = self._constraint_arg(constraint)
         ss = self._stop_sequences_arg(stop_sequences)
+        bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
         self._check_tokens(prompt)
+        self._check_conversation(prompt)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
         L = padded_length(len(prompt))
@@ -1735,12 +1888,14 @@ class TenantSession:
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
         self._context(t, prompt, pp)
         self._write_constraint(t, con, stops)
+        self._write_bans(t, bp, prompt, stops)
         self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con, ss=ss)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
     def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
+               presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
+               bad_words=(), min_new_tokens=0):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -1757,7 +1912,11 @@ class TenantSession:
         constraint as in submit: it constrains THIS turn's tokens only, from its start state; None leaves the turn free.
         stop_sequences as in submit: they replace the turn before's, and matching restarts with the turn, as result() does -- tokens of earlier
         turns never take part.  A tenant retired by reason 16 is extended like one retired by a stop token: its last token, the one that
-        completed the sequence, is the one not yet in the cache."""
+        completed the sequence, is the one not yet in the cache.
+        no_repeat_ngram_size / bad_words / min_new_tokens as in submit (this turn's own).  The history they look at is the WHOLE conversation:
+        what the tenant was submitted, every earlier turn's emitted tokens and new tokens, then `tokens`, then this turn's own -- an n-gram seen
+        only in turn one is banned in turn two; min_new_tokens counts this turn's tokens.  A ban session reads the earlier turn's tokens back
+        (one more host read) to keep that history."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
@@ -1768,26 +1927,36 @@ class TenantSession:
         pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
         con = self._check_constraint(self._constraint_arg(constraint), stops)
         ss = self._stop_sequences_arg(stop_sequences)
+        bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
         self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
+        conv = None
+        if self.bans:                                 # the conversation so far: what it held, the turn before's tokens, the new ones
+            conv = self._ctx_tokens[t] + self.result(t)[0].tolist() + tokens
+            self._check_conversation(conv)
         ids = torch.tensor([[last] + tokens], dtype=torch.long).to(dec.dev)
         kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
         self._context(t, [last] + tokens, pp, fold=True)
         self._write_constraint(t, con, stops)
+        self._write_bans(t, bp, conv, stops)
         self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con, ss=ss)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
-                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=()):
+                   presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
+                   bad_words=(), min_new_tokens=0):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
         common padded length.  temperature / top_k / top_p / seed and the four penalty arguments: each one value for all (a logit_bias mapping
         is one value) or a list with one value per tenant.  constraint: None or one TokenAutomaton for all, or a list with one (or None) per
         tenant.  stop_sequences: one list of token-id lists for all, or a list with one such list per tenant; the two are told apart by depth
-        (_per_tenant_stop_sequences)."""
+        (_per_tenant_stop_sequences).  no_repeat_ngram_size / min_new_tokens: one value for all or a list with one per tenant; bad_words: one list
+        of token-id lists for all or a list with one such list per tenant, told apart as stop_sequences are."""
         dec = self.dec
         assert max_new_tokens >= 1
+        bps = [self._ban_params(*a) for a in zip(self._per_tenant(no_repeat_ngram_size), self._per_tenant_bad_words(bad_words),
+                                                 self._per_tenant(min_new_tokens))]
         sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
                                              self._per_tenant(seed))]
         pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
@@ -1796,6 +1965,7 @@ class TenantSession:
         sss = [self._stop_sequences_arg(v) for v in self._per_tenant_stop_sequences(stop_sequences)]
         for p_ in prompts:
             self._check_tokens(p_)
+            self._check_conversation(p_)
         if bool(self.active_flags.any()):
             raise RuntimeError("a tenant is still generating")
         stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
@@ -1809,6 +1979,7 @@ class TenantSession:
         for t in range(self.T):
             self._context(t, prompts[t], pps[t])
             self._write_constraint(t, cons[t], stops[t])
+            self._write_bans(t, bps[t], prompts[t], stops[t])
         first = self._first_tokens(logits, sps, L)
         for t in range(self.T):
             self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t], ss=sss[t])
@@ -1826,6 +1997,9 @@ class TenantSession:
             logits = ops.step_penalize(raw, self.plogits, self.hist, self.tok, self.active_flags, self.pen, self.bias_id, self.bias_val)
         if self.constraints:                          # masks the (penalised) row by each tenant's automaton state; the state itself moves below
             logits = ops.step_constrain(logits, self.clogits, self.c_state, self.c_off, self.c_tok, self.c_acc, self.stop_ids, self.active_flags)
+        if self.bans:                                 # masks what the tenant's own history forbids; wins over a positive bias and a constraint's edge
+            logits = ops.step_ban(logits, self.blogits, self.ctx, self.ctx_len, self.out, self.n, self.ban_ngram, self.ban_tok, self.ban_len,
+                                  self.ban_min, self.stop_ids, self.active_flags)
         if self.sampling:
             ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
                                 self.temperature, self.top_k, self.top_p, self.seed)
@@ -1856,12 +2030,14 @@ class TenantSession:
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
         and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
         one more launch in front of the last; constraints: one more in front of the last and one behind it; stop sequences: one more at the very end, on a table of the
-        session's two sizes) alone."""
+        session's two sizes; bans: one more in front of the step end, on a table of the session's two sizes) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
                self.sampling, self.logprobs, self.penalties, self.constraints)
         if self.stop_sequences:                       # (a session without them keeps the key it had)
             key = key + (True, self.ss_tok.shape[1], self.ss_tok.shape[2])
+        if self.bans:                                 # (likewise; the launch keeps no counter, so _state() gains nothing)
+            key = key + ("bans", self.ban_tok.shape[1], self.ban_tok.shape[2])
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:

@@ -550,6 +550,83 @@ def step_stop_sequences(out, n, ss_n, seq_tok, seq_len, hit, hold, active, done)
                                                ptr(active), ptr(done), T, stream_ptr()), "srv_step_stop_sequences")
 
 
+BAN_NGRAM_MAX = 8          # include/bitdelta_hip.h (BD_BAN_NGRAM_MAX / BD_BAN_WORDS_MAX / BD_BAN_WORD_LEN_MAX / BD_BAN_STOP_MAX)
+BAN_WORDS_MAX = 64
+BAN_WORD_LEN_MAX = 32
+BAN_STOP_MAX = 64
+
+
+def _ban_args(logits, out, ctx, ctx_len, toks, n, ban_ngram, ban_tok, ban_len, ban_min, stop_ids):
+    """the checks ban_rows and step_ban share; returns (out, Lc, toks pointer, s_tok, tok_cap, n pointer, Q, W, ns, stop_ids pointer)"""
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and logits.dtype in (torch.float16, torch.bfloat16)
+    if out is None:
+        out = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
+    require_gpu(out, ctx, ctx_len, ban_ngram, ban_tok, ban_len, ban_min)
+    assert out.shape == (R, V) and out.dtype == logits.dtype and out.stride(1) == 1
+    assert ctx.dim() == 2 and ctx.shape[0] == R and ctx.dtype == torch.int32 and ctx.is_contiguous()
+    Lc = ctx.shape[1]
+    assert ban_tok.dim() == 3 and ban_tok.shape[0] == R and ban_tok.dtype == torch.int32 and ban_tok.is_contiguous()
+    Q, W = ban_tok.shape[1:]
+    assert 1 <= Q <= BAN_WORDS_MAX and 1 <= W <= BAN_WORD_LEN_MAX
+    assert ban_len.shape == (R, Q) and ban_len.dtype == torch.int32 and ban_len.is_contiguous()
+    for x in (ctx_len, ban_ngram, ban_min):
+        assert x.dtype == torch.int32 and x.is_contiguous() and x.numel() == R
+    tp, s_tok, cap, np_ = None, 0, 0, None
+    if n is not None:
+        require_gpu(toks, n)
+        assert n.dtype == torch.long and n.is_contiguous() and n.numel() == R
+        assert toks.dim() == 2 and toks.dtype == torch.long and toks.shape[0] == R and (toks.stride(1) == 1 or toks.shape[1] <= 1)
+        cap = toks.shape[1]
+        s_tok = toks.stride(0) if R > 1 else cap
+        assert s_tok >= cap
+        tp, np_ = ptr(toks), ptr(n)
+    if stop_ids is None or stop_ids.shape[1] == 0:
+        return out, Lc, tp, s_tok, cap, np_, Q, W, 0, None
+    require_gpu(stop_ids)
+    ns = stop_ids.shape[1]
+    assert stop_ids.shape == (R, ns) and ns <= BAN_STOP_MAX and stop_ids.dtype == torch.long and stop_ids.is_contiguous()
+    return out, Lc, tp, s_tok, cap, np_, Q, W, ns, ptr(stop_ids)
+
+
+def ban_rows(logits, ctx, ctx_len, ban_ngram, ban_tok, ban_len, ban_min, stop_ids=None, toks=None, n=None, out=None):
+    """The copy of logits [R, V] (16-bit, V % 8 == 0) with every token -inf that the row's no-repeat n-gram size, bad words or minimum turn length
+    ban after its history, every other element keeping its bits; include/bitdelta_hip.h (bd_srv_ban_rows) is the definition.  The history of
+    row r is ctx[r, :ctx_len[r]] (int32 [R, Lc], int32 [R]) followed by toks[r, :n[r]] (long [R, cap], rows may be strided; long [R]); n=None:
+    no turn tokens yet (admission).  ban_ngram int32 [R] (0 = off); ban_tok int32 [R, Q, W] with ban_len int32 [R, Q] (0 = an unused slot);
+    ban_min int32 [R]; stop_ids long [R, ns <= 64] (-1: an empty slot; None: no list), banned while n < ban_min.  Rows of logits may be strided
+    (stride % 8 == 0, 16-byte aligned; logits of another layout are copied first, as in constrain_rows); out: a tensor of the logits' shape and
+    dtype to write into instead of a new one."""
+    require_gpu(logits)
+    assert logits.dim() == 2
+    R, V = logits.shape
+    sl = logits.stride(0) if R > 1 else V
+    if logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16:             # (token_logprobs' rule: such rows are copied first)
+        logits, sl = logits.contiguous(), V
+    out, Lc, tp, s_tok, cap, np_, Q, W, ns, sp = _ban_args(logits, out, ctx, ctx_len, toks, n, ban_ngram, ban_tok, ban_len, ban_min, stop_ids)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_ban_rows(ptr(logits), sl, V, ptr(out), out.stride(0) if R > 1 else V, ptr(ctx) if Lc else None, Lc, ptr(ctx_len), tp,
+                                    s_tok, cap, np_, ptr(ban_ngram), ptr(ban_tok), ptr(ban_len), Q, W, ptr(ban_min), sp, ns, R,
+                                    DTYPE_CODE[logits.dtype], stream_ptr()), "srv_ban_rows")
+    return out
+
+
+def step_ban(logits, out, ctx, ctx_len, toks, n, ban_ngram, ban_tok, ban_len, ban_min, stop_ids, active):
+    """ban_rows inside a ragged decode step, logits [T, V] -> out [T, V], behind the lm_head, step_penalize and step_constrain and in front of the
+    step end, which then reads `out`; toks / n are the step end's output rows and token counts.  An inactive tenant's row of out is not touched.
+    The launch only reads: it keeps no counter.  active [T] bool / uint8."""
+    require_gpu(logits, active)
+    assert n is not None
+    out, Lc, tp, s_tok, cap, np_, Q, W, ns, sp = _ban_args(logits, out, ctx, ctx_len, toks, n, ban_ngram, ban_tok, ban_len, ban_min, stop_ids)
+    T, V = logits.shape
+    assert active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == T
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_ban(ptr(logits), logits.stride(0), V, ptr(out), out.stride(0), ptr(ctx) if Lc else None, Lc, ptr(ctx_len), tp,
+                                    s_tok, cap, np_, ptr(ban_ngram), ptr(ban_tok), ptr(ban_len), Q, W, ptr(ban_min), sp, ns,
+                                    ptr(active), T, DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_ban")
+    return out
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

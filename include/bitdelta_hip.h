@@ -511,6 +511,59 @@ int bd_srv_step_constrain_advance(const int64_t* tok, const int64_t* n, int64_t*
 int bd_srv_step_stop_sequences(const int64_t* out, int64_t s_out, int out_cap, const int64_t* n, int64_t* ss_n, const int32_t* seq_tok,
                                const int32_t* seq_len, int Q, int W, int32_t* hit, int32_t* hold, uint8_t* active, uint8_t* done, int T,
                                void* stream);
+/* bd_srv_ban_rows: the hard bans that depend on what a request has already written -- Hugging Face's NoRepeatNGramLogitsProcessor
+ * (no_repeat_ngram_size), NoBadWordsLogitsProcessor (bad_words_ids; vLLM's bad_words) and MinNewTokensLengthLogitsProcessor (min_new_tokens)
+ * -- as one masked copy of the row.  Per row r:
+ *   ctx        int32 [R, Lc], ctx_len int32 [R]: the conversation's real tokens before this turn (a prompt without its left pads; on a later
+ *              turn everything before it, the earlier turns' emitted tokens included).
+ *   toks       int64 [R, tok_cap] with row stride s_tok (elements), n int64 [R]: this turn's emitted tokens toks[r, 0:n[r]] (the step end's `out`
+ *              and `n`).  n == NULL means no token yet, n = 0 for every row (admission); toks is then not read and may be NULL.
+ *   ban_ngram  int32 [R]: the no-repeat n-gram size g, 1 .. BD_BAN_NGRAM_MAX; 0 = off.
+ *   ban_tok    int32 [R, Q, W], ban_len int32 [R, Q]: the bad words, sequence q in ban_tok[r, q, 0:ban_len[r, q]]; a length 0 = an unused slot.
+ *   ban_min    int32 [R]: the turn's minimum length (min_new_tokens).
+ *   stop_ids   int64 [R, ns]: the request's stop ids, -1 = an empty slot.
+ * The history is h[0:m) = ctx[r, 0:ctx_len[r]] followed by toks[r, 0:n[r]], m = ctx_len[r] + n[r].  Token v in [0, V) is BANNED when
+ *   n-gram:     g >= 1, m >= g - 1, and some i with 0 <= i <= m - g has h[i : i + g - 1] == h[m - g + 1 : m] and h[i + g - 1] == v (the last
+ *               g - 1 tokens occurred before, followed by v; with g == 1 every token of the history is banned); or
+ *   bad word:   some q with L = ban_len[r, q] has ban_tok[r, q, L - 1] == v and either L == 1, or L > 1, m >= L - 1 and
+ *               h[m - L + 1 : m] == ban_tok[r, q, 0 : L - 1]; or
+ *   early stop: n[r] < ban_min[r] and v == stop_ids[r, j] for some j.
+ * out[v] = -inf (the dtype's bit pattern) for a banned v, and l[v], the same 16 bits, otherwise: -0, subnormals, NaN payloads and +-inf pass
+ * through (no float is made of a logit).  An id outside [0, V) bans nothing.  With m >= the longest bad word this is Hugging Face's rule
+ * (transformers 5) for all three processors.  Below that length it deviates ON PURPOSE: HF skips a bad word with L > m, here its prefix is
+ * matched from m >= L - 1 on, so a two-token bad word right behind a one-token prompt is still banned.  min_new_tokens holds back stop IDS only
+ * -- neither a stop sequence (bd_srv_step_stop_sequences) nor a constraint's final state.  A row whose bans, alone or with a constraint, leave no
+ * finite element is the caller's error, as a -inf bias on every token is: nothing is defined for it.
+ * Device values the host could not have written are neutralised: ctx_len is clamped into [0, Lc], n into [0, tok_cap], a g outside
+ * 0 .. BD_BAN_NGRAM_MAX is off, a ban_len outside 0 .. W is an unused slot.  History elements are compared as 64-bit integers.  An out element is
+ * a pure function of (l[v], v, h, the row's parameters and tables): no global atomics, no two blocks write one address, nothing depends on R, on
+ * the strides, on thread or block order, or on graph or eager execution, and the launch keeps no counter.  tests/ban_ref.py restates the
+ * definition.
+ * logits / out [R, V] fp16 / bf16 with row strides sl / so (elements); elements V .. stride - 1 of a row are neither read nor written.  The
+ * other arrays are contiguous but for toks' row stride.  Checked before any device call, in this order: R < 0, V < 1, V > 2^22 ->
+ * BD_E_BAD_SHAPE; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE; R == 0 -> BD_OK, nothing launched; Q outside 1 .. BD_BAN_WORDS_MAX, W outside
+ * 1 .. BD_BAN_WORD_LEN_MAX, ns outside 0 .. BD_BAN_STOP_MAX, Lc < 0, tok_cap < 0, s_tok < tok_cap, Lc + tok_cap > 2^31 - 1 or R > 65535 ->
+ * BD_E_BAD_SHAPE; a needed pointer NULL (ctx only when Lc > 0, stop_ids when ns > 0, toks when n is given and tok_cap > 0) -> BD_E_NULL; V % 8,
+ * a stride % 8 or < V, logits / out not 16-byte, toks / n / stop_ids not 8-byte, the int32 arrays not 4-byte aligned -> BD_E_BAD_SHAPE.
+ * Several blocks per row: grid (ceil(V / 2048), R), 256 threads.  Every block walks the row's history (the n-gram tail staged once in LDS,
+ * candidates rejected on their last token first), the bad-word table and the stop ids, and sets the bans of its own 2048 elements in a
+ * 256-byte LDS bitmap; then one 16-byte load, the mask and one 16-byte store per thread. */
+#define BD_BAN_NGRAM_MAX 8
+#define BD_BAN_WORDS_MAX 64
+#define BD_BAN_WORD_LEN_MAX 32
+#define BD_BAN_STOP_MAX 64
+int bd_srv_ban_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* ctx, int Lc, const int32_t* ctx_len,
+                    const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram, const int32_t* ban_tok,
+                    const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids, int ns, int R, int dtype,
+                    void* stream);
+/* bd_srv_step_ban: bd_srv_ban_rows inside a ragged decode step, behind the lm_head, bd_srv_step_penalize and bd_srv_step_constrain (whose row it
+ * then reads, so a ban wins over a positive logit bias) and in front of bd_srv_step_end_ragged / bd_srv_step_end_sample (which then read
+ * `out`); toks / n are the step end's output rows and counts BEFORE it runs, active bytes [T].  An inactive tenant's out row is not touched and
+ * nothing of it is read.  Checks as above with T for R; n or active NULL -> BD_E_NULL. */
+int bd_srv_step_ban(const void* logits, int64_t sl, int V, void* out, int64_t so, const int32_t* ctx, int Lc, const int32_t* ctx_len,
+                    const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram, const int32_t* ban_tok,
+                    const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids, int ns, const uint8_t* active, int T,
+                    int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
