@@ -2,7 +2,8 @@
 // Llama / Mistral decoder layer is what it calls between two of the reference's Linears).  These three kernels are NOT the hot
 // path -- they move a few hundred KB per layer -- but at decode every torch op is a launch, and a layer written with stock ops is
 // ~30 launches around 4 weight-streaming Linears.  HBM/latency-bound, elementwise or tiny reductions; fp32 math, results rounded
-// where the torch ops they replace round (noted per kernel), so they are compared against those ops in tests/test_gpu_serving.py.
+// where the torch ops they replace round (noted per kernel), so they are compared against those ops in tests/test_gpu_serving.py, and
+// element by element against fp64 models with exactly these rounding points in tests/test_gpu_glue_exact.py (models: tests/glue_ref.py).
 //
 //   rmsnorm_tenant_kernel   y[r] = w[tenant(r)] * round16(x[r] * rsqrt(mean(x[r]^2) + eps))        (HF RMSNorm, per-tenant weight)
 //   swiglu_kernel           y = round16(silu(g)) * u     from the fused gate|up output               (HF MLP act_fn(gate) * up)
