@@ -74,6 +74,12 @@ SIGNATURES = {
     "bd_srv_rope": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_decode_attention": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),
     "bd_srv_decode_attention_ragged": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),
+    # the four entries above with a tenant stride of the rotary tables behind sin_t (0 = one shared table)
+    "bd_srv_rope_kv_append_tab": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
+    "bd_srv_rope_tab": (_ci, [_vp, _vp, _vp, _i64, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
+    "bd_srv_decode_attention_tab": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),
+    "bd_srv_decode_attention_ragged_tab": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64,
+                                                 _vp]),
     "bd_srv_decode_attention_workspace_bytes": (_i64, [_ci, _ci, _ci, _ci, _ci]),
     "bd_srv_prefill_attention": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                        _vp, ctypes.c_float, _ci, _ci, _vp]),

@@ -1782,9 +1782,14 @@ extern "C" int bd_srv_swiglu(const void* G, const void* U, void* Y, int rows, in
     return launch_status();
 }
 
-extern "C" int bd_srv_rope(void* X, const void* cos_t, const void* sin_t, int rows, int heads, int head_dim, int64_t sx, int seq,
-                           int pos0, int dtype, void* stream) {
-    if (rows < 0 || heads < 1 || seq < 1 || pos0 < 0) return BD_E_BAD_SHAPE;
+// Per-tenant rotary tables (the *_tab entries): s_tab is the tenant stride of cos_t / sin_t in elements, 0 = one table for every tenant.  Each
+// shared-table entry is its *_tab sibling at s_tab = 0: one launcher and one kernel per pair.  The stride keeps every tenant's rows 16-byte
+// aligned (the rope kernels read the tables in 16-byte chunks), so it is a multiple of 8 elements.
+static inline bool tab_stride_ok(int64_t s_tab) { return s_tab >= 0 && s_tab % 8 == 0; }
+
+extern "C" int bd_srv_rope_tab(void* X, const void* cos_t, const void* sin_t, int64_t s_tab, int rows, int heads, int head_dim, int64_t sx,
+                               int seq, int pos0, int dtype, void* stream) {
+    if (rows < 0 || heads < 1 || seq < 1 || pos0 < 0 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (rows == 0) return BD_OK;
     if (!X || !cos_t || !sin_t) return BD_E_NULL;
@@ -1792,16 +1797,21 @@ extern "C" int bd_srv_rope(void* X, const void* cos_t, const void* sin_t, int ro
     hipStream_t st = (hipStream_t)stream;
     if (dtype == BD_BF16)
         hipLaunchKernelGGL((rope_kernel<DT_BF16>), dim3(rows), dim3(256), 0, st, (unsigned short*)X, (const unsigned short*)cos_t,
-                           (const unsigned short*)sin_t, heads, (long long)sx, seq, pos0);
+                           (const unsigned short*)sin_t, (long long)s_tab, heads, (long long)sx, seq, pos0);
     else
         hipLaunchKernelGGL((rope_kernel<DT_F16>), dim3(rows), dim3(256), 0, st, (unsigned short*)X, (const unsigned short*)cos_t,
-                           (const unsigned short*)sin_t, heads, (long long)sx, seq, pos0);
+                           (const unsigned short*)sin_t, (long long)s_tab, heads, (long long)sx, seq, pos0);
     return launch_status();
 }
 
-extern "C" int bd_srv_rope_kv_append(void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, int T, int S, int H, int KVH,
-                                     int head_dim, int64_t sx, int Lc, int pos0, int dtype, void* stream) {
-    if (T < 0 || S < 0 || H < 1 || KVH < 1 || pos0 < 0 || Lc < 1) return BD_E_BAD_SHAPE;
+extern "C" int bd_srv_rope(void* X, const void* cos_t, const void* sin_t, int rows, int heads, int head_dim, int64_t sx, int seq,
+                           int pos0, int dtype, void* stream) {
+    return bd_srv_rope_tab(X, cos_t, sin_t, 0, rows, heads, head_dim, sx, seq, pos0, dtype, stream);
+}
+
+extern "C" int bd_srv_rope_kv_append_tab(void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, int T, int S,
+                                         int H, int KVH, int head_dim, int64_t sx, int Lc, int pos0, int dtype, void* stream) {
+    if (T < 0 || S < 0 || H < 1 || KVH < 1 || pos0 < 0 || Lc < 1 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (T == 0 || S == 0) return BD_OK;
     if (!QKV || !cos_t || !sin_t || !kcache || !vcache) return BD_E_NULL;
@@ -1811,13 +1821,18 @@ extern "C" int bd_srv_rope_kv_append(void* QKV, const void* cos_t, const void* s
     hipStream_t st = (hipStream_t)stream;
     if (dtype == BD_BF16)
         hipLaunchKernelGGL((rope_kv_append_kernel<DT_BF16>), dim3((unsigned)(T * S)), dim3(256), 0, st, (unsigned short*)QKV,
-                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (unsigned short*)kcache, (unsigned short*)vcache, H, KVH,
-                           (long long)sx, S, pos0, Lc);
+                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (long long)s_tab, (unsigned short*)kcache,
+                           (unsigned short*)vcache, H, KVH, (long long)sx, S, pos0, Lc);
     else
         hipLaunchKernelGGL((rope_kv_append_kernel<DT_F16>), dim3((unsigned)(T * S)), dim3(256), 0, st, (unsigned short*)QKV,
-                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (unsigned short*)kcache, (unsigned short*)vcache, H, KVH,
-                           (long long)sx, S, pos0, Lc);
+                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (long long)s_tab, (unsigned short*)kcache,
+                           (unsigned short*)vcache, H, KVH, (long long)sx, S, pos0, Lc);
     return launch_status();
+}
+
+extern "C" int bd_srv_rope_kv_append(void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, int T, int S, int H, int KVH,
+                                     int head_dim, int64_t sx, int Lc, int pos0, int dtype, void* stream) {
+    return bd_srv_rope_kv_append_tab(QKV, cos_t, sin_t, 0, kcache, vcache, T, S, H, KVH, head_dim, sx, Lc, pos0, dtype, stream);
 }
 
 extern "C" int bd_srv_step_begin(const void* embed, int64_t sEt, int64_t sEv, const int64_t* tok, void* X, int64_t sx, void* valid, int Lc,
@@ -1968,19 +1983,22 @@ extern "C" int64_t bd_srv_decode_attention_workspace_bytes(int T, int H, int KVH
 
 // bd_srv_decode_attention and its ragged form: ONE body, so validation, split rule, workspace layout and depth rule cannot drift apart (a ragged
 // launch at equal positions has the scalar launch's geometry).  RAGGED: pos is [T] and `active` [T] bytes.
+// s_tab: tenant stride of the rotary tables (the *_tab entries; the shared-table entries pass 0 and tab_entry = false, which keeps their
+// validation as it was: they never asked for aligned tables, the kernel reads them element by element).
 template <bool RAGGED>
-static int decode_attention_launch(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
+static int decode_attention_launch(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, bool tab_entry, void* kcache, void* vcache,
                                    void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
                                    int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
-    if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1) return BD_E_BAD_SHAPE;
+    if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (T == 0) return BD_OK;
     if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !valid || !pos || !out || (RAGGED && !active)) return BD_E_NULL;
     const int G = H / KVH;
-    if (head_dim != 128 || (G != 1 && G != 4 && G != 8) || s_qkv % 8 || !aligned16(QKV) || !aligned16(kcache) || !aligned16(vcache))
+    if (head_dim != 128 || (G != 1 && G != 4 && G != 8) || s_qkv % 8 || !aligned16(QKV) || !aligned16(kcache) || !aligned16(vcache) ||
+        (tab_entry && (!aligned16(cos_t) || !aligned16(sin_t))))
         return BD_E_BAD_SHAPE;                         // other head geometries: the caller keeps its torch attention
     AttnParams p;
-    p.qkv = (const unsigned short*)QKV; p.cos = (const unsigned short*)cos_t; p.sin = (const unsigned short*)sin_t;
+    p.qkv = (const unsigned short*)QKV; p.cos = (const unsigned short*)cos_t; p.sin = (const unsigned short*)sin_t; p.s_tab = s_tab;
     p.kc = (unsigned short*)kcache; p.vc = (unsigned short*)vcache; p.valid = (unsigned char*)valid; p.pos = (const long long*)pos;
     p.active = (const unsigned char*)active;
     p.out = (unsigned short*)out; p.T = T; p.H = H; p.KVH = KVH; p.Lc = Lc; p.s_qkv = s_qkv; p.s_out = s_out;
@@ -2026,15 +2044,30 @@ static int decode_attention_launch(const void* QKV, const void* cos_t, const voi
 extern "C" int bd_srv_decode_attention(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
                                        void* valid, const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
                                        int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
-    return decode_attention_launch<false>(QKV, cos_t, sin_t, kcache, vcache, valid, pos, nullptr, out, T, H, KVH, head_dim, Lc, s_qkv, s_out, dtype,
-                                          ws, ws_bytes, stream);
+    return decode_attention_launch<false>(QKV, cos_t, sin_t, 0, false, kcache, vcache, valid, pos, nullptr, out, T, H, KVH, head_dim, Lc, s_qkv, s_out,
+                                          dtype, ws, ws_bytes, stream);
 }
 
 extern "C" int bd_srv_decode_attention_ragged(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache,
                                               void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim,
                                               int Lc, int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
-    return decode_attention_launch<true>(QKV, cos_t, sin_t, kcache, vcache, valid, pos, active, out, T, H, KVH, head_dim, Lc, s_qkv, s_out, dtype,
-                                         ws, ws_bytes, stream);
+    return decode_attention_launch<true>(QKV, cos_t, sin_t, 0, false, kcache, vcache, valid, pos, active, out, T, H, KVH, head_dim, Lc, s_qkv, s_out,
+                                         dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int bd_srv_decode_attention_tab(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                           void* valid, const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                           int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
+    return decode_attention_launch<false>(QKV, cos_t, sin_t, s_tab, true, kcache, vcache, valid, pos, nullptr, out, T, H, KVH, head_dim, Lc, s_qkv,
+                                          s_out, dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int bd_srv_decode_attention_ragged_tab(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                                  void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH,
+                                                  int head_dim, int Lc, int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes,
+                                                  void* stream) {
+    return decode_attention_launch<true>(QKV, cos_t, sin_t, s_tab, true, kcache, vcache, valid, pos, active, out, T, H, KVH, head_dim, Lc, s_qkv,
+                                         s_out, dtype, ws, ws_bytes, stream);
 }
 
 extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,

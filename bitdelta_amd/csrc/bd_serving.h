@@ -727,13 +727,15 @@ __global__ void __launch_bounds__(256) step_end_sample_kernel(const unsigned sho
 // the sign folded into `sin`: out[d] = round16(round16(x[d] * cos[d]) + x[d +- 64] * sin[d])  -- the rounding points of the stock
 // composition `torch.addcmul(x * cos, rot, sin)`, which costs five passes (cat, mul, addcmul + two temporaries) instead of one.
 // Position of row r = pos0 + r % seq.  One block per row, one thread per (head, 8 dims of the lower half + their partners).
+// s_tab: tenant stride of the tables in elements (0 = one shared table); the tenant of row r is r / seq.
 template <int DT>
 __global__ void __launch_bounds__(256) rope_kernel(unsigned short* __restrict__ x, const unsigned short* __restrict__ cos_t,
-                                                   const unsigned short* __restrict__ sin_t, int heads, long long sx, int seq, int pos0) {
+                                                   const unsigned short* __restrict__ sin_t, long long s_tab, int heads, long long sx, int seq,
+                                                   int pos0) {
     const int r = blockIdx.x;
-    const long long pos = pos0 + r % seq;
-    const unsigned short* cs = cos_t + pos * 128;
-    const unsigned short* sn = sin_t + pos * 128;
+    const long long tab = (r / seq) * s_tab + (long long)(pos0 + r % seq) * 128;
+    const unsigned short* cs = cos_t + tab;
+    const unsigned short* sn = sin_t + tab;
     for (int i = threadIdx.x; i < heads * 8; i += 256) {
         const int h = i >> 3, d0 = (i & 7) * 8;
         unsigned short* px = x + (long long)r * sx + h * 128;
@@ -764,15 +766,16 @@ __global__ void __launch_bounds__(256) rope_kernel(unsigned short* __restrict__ 
 // 128] (in place -- the prefill attention kernel reads q / k / v from that buffer), and the rotated k rows and the v rows of every token also go to
 // the caches [T, KVH, Lc, 128] at positions pos0 .. pos0 + S - 1: the two strided torch copies `cache[:, :, :S] = k.transpose(1, 2)` (6.3 + 5.6 us
 // per layer on a 6 x 64-token request) ride on a launch that already has the rows in registers.  One block per token row.
+// s_tab: tenant stride of the tables in elements (0 = one shared table).
 template <int DT>
 __global__ void __launch_bounds__(256) rope_kv_append_kernel(unsigned short* __restrict__ x, const unsigned short* __restrict__ cos_t,
-                                                             const unsigned short* __restrict__ sin_t, unsigned short* __restrict__ kc,
-                                                             unsigned short* __restrict__ vc, int H, int KVH, long long sx, int seq, int pos0,
-                                                             int Lc) {
+                                                             const unsigned short* __restrict__ sin_t, long long s_tab,
+                                                             unsigned short* __restrict__ kc, unsigned short* __restrict__ vc, int H, int KVH,
+                                                             long long sx, int seq, int pos0, int Lc) {
     const int r = blockIdx.x, t = r / seq;
     const long long pos = pos0 + (r - t * seq);
-    const unsigned short* cs = cos_t + pos * 128;
-    const unsigned short* sn = sin_t + pos * 128;
+    const unsigned short* cs = cos_t + t * s_tab + pos * 128;
+    const unsigned short* sn = sin_t + t * s_tab + pos * 128;
     unsigned short* row = x + (long long)r * sx;
     const int nrope = (H + KVH) * 8, ntot = nrope + KVH * 16;
     for (int i = threadIdx.x; i < ntot; i += 256) {
@@ -814,7 +817,7 @@ __global__ void __launch_bounds__(256) rope_kv_append_kernel(unsigned short* __r
 struct AttnParams {
     const unsigned short* qkv;     // [T, (H + 2*KVH) * 128]: q heads, then k heads, then v heads (the fused q+k+v Linear's output row)
     const unsigned short* cos;     // [Lmax, 128] RoPE tables in the activation dtype, rotate-half sign folded into `sin`
-    const unsigned short* sin;
+    const unsigned short* sin;     // (s_tab != 0: [T, Lmax, 128], tenant t's rows at + t * s_tab)
     unsigned short* kc;            // KV cache [T, KVH, Lc, 128]
     unsigned short* vc;
     unsigned char* valid;          // [T, Lc] key-validity bytes (left padding = 0); the new position is set here
@@ -827,6 +830,7 @@ struct AttnParams {
     float* ws;                     // nsplit > 1: partial (acc[128], max, sum) per (tenant, kv head, split, query head): [.., G, 130] fp32
     unsigned* tickets;             // nsplit > 1: one arrival counter per (tenant, kv head), zero when the launch is enqueued
     int nsplit;                    // key range split over blockIdx.y (one CU streams only ~12-25 GB/s: 48 blocks cannot feed on HBM)
+    long long s_tab;               // tenant stride of cos / sin in elements; 0 = one table for every tenant
 };
 
 // One block of 8 waves per (tenant, kv head): its G = H / KVH query heads share the K / V stream.  Lane (kq = l >> 4, d8 = l & 15)
@@ -875,8 +879,9 @@ __global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
         pos = *p.pos;
     }
     const unsigned short* row = p.qkv + (long long)t * p.s_qkv;
-    const unsigned short* cs = p.cos + pos * HD;
-    const unsigned short* sn = p.sin + pos * HD;
+    // (t comes from blockIdx and s_tab from the kernel arguments: the tenant's table offset is scalar arithmetic next to pos * HD, in both forms)
+    const unsigned short* cs = p.cos + t * p.s_tab + pos * HD;
+    const unsigned short* sn = p.sin + t * p.s_tab + pos * HD;
     unsigned short* kbase = p.kc + ((long long)t * p.KVH + kvh) * p.Lc * HD;
     unsigned short* vbase = p.vc + ((long long)t * p.KVH + kvh) * p.Lc * HD;
     const unsigned char* vld = p.valid + (long long)t * p.Lc;

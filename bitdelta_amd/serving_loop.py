@@ -369,8 +369,107 @@ class FusedDeltaLinear(nn.Module):
         return self.weight.numel() * (1 if self.base_int8 else self.weight.element_size()) + self.mask.numel() * 4
 
 
-def _rope_tables(length, dim, device, dtype, base=10000.0):
-    inv = 1.0 / (base ** (torch.arange(0, dim, 2, device=device, dtype=torch.float32) / dim))
+class RopeSpec(collections.namedtuple("RopeSpec", "theta kind factor low_freq_factor high_freq_factor original_max_position_embeddings inv_freq")):
+    """One fine-tune's rotary embedding as data (rope_spec makes and validates it): hashable, compared by value."""
+    __slots__ = ()
+
+
+_ROPE_REFUSED = {
+    "dynamic": "its table depends on the sequence length, and the tables here are built once",
+    "yarn": "it needs an attention factor other than 1 on cos / sin",
+    "longrope": "it needs an attention factor other than 1 and switches tables with the sequence length",
+}
+
+
+def rope_spec(theta=10000.0, scaling=None, inv_freq=None):
+    """A tenant's rotary embedding, validated on the host: a hashable RopeSpec.  theta: HF's `rope_theta`, finite and > 0.  scaling: HF's
+    `rope_scaling` / `rope_parameters` dict or None -- `rope_type` (or the older key `type`) "default", "linear" (`factor` >= 1: every
+    frequency divided by it) or "llama3" (`factor` >= 1, `low_freq_factor`, `high_freq_factor`, `original_max_position_embeddings`: the
+    frequency-band rule).  inv_freq: instead of the formula, the head_dim / 2 inverse frequencies themselves (any fp32 sequence or tensor;
+    finite), for a static scheme this module does not spell; not together with scaling.  Refused (ValueError): "dynamic" (the table
+    depends on the sequence length), "yarn" and "longrope" (they scale cos / sin by an attention factor other than 1), unknown types,
+    factor < 1, a theta that is not finite and positive, a bad inv_freq.  Its length is checked against the head size where the spec
+    meets one (rope_inv_freq)."""
+    try:
+        th = float(theta)
+    except (TypeError, ValueError):
+        raise ValueError("rope theta = %r: a number is required" % (theta,))
+    if not (math.isfinite(th) and th > 0.0):
+        raise ValueError("rope theta = %r: a finite value > 0 is required" % (theta,))
+    if inv_freq is not None:
+        if scaling is not None:
+            raise ValueError("inv_freq and scaling together: the caller's frequencies already are the scaled ones")
+        try:
+            vals = torch.as_tensor(inv_freq).detach().to("cpu", torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("inv_freq = %r: a vector of numbers is required" % (inv_freq,))
+        if vals.dim() != 1 or vals.numel() == 0 or not bool(torch.isfinite(vals).all()):
+            raise ValueError("inv_freq: a vector of head_dim / 2 finite values is required")
+        return RopeSpec(th, "inv_freq", 1.0, None, None, None, tuple(vals.tolist()))
+    if scaling is None:
+        return RopeSpec(th, "default", 1.0, None, None, None, None)
+    if not isinstance(scaling, collections.abc.Mapping):
+        raise ValueError("rope scaling = %r: HF's rope_scaling dict is required" % (scaling,))
+    kind = scaling.get("rope_type", scaling.get("type", "default"))
+    if kind in _ROPE_REFUSED:
+        raise ValueError("rope scaling type %r is not supported: %s" % (kind, _ROPE_REFUSED[kind]))
+    if kind not in ("default", "linear", "llama3"):
+        raise ValueError("rope scaling type %r: \"default\", \"linear\" or \"llama3\" is required" % (kind,))
+    if kind == "default":
+        return RopeSpec(th, "default", 1.0, None, None, None, None)
+
+    def number(key):
+        try:
+            v = float(scaling[key])
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("rope scaling %r needs a number %r" % (kind, key))
+        if not math.isfinite(v):
+            raise ValueError("rope scaling %s = %r: a finite value is required" % (key, scaling[key]))
+        return v
+    factor = number("factor")
+    if factor < 1.0:
+        raise ValueError("rope scaling factor = %r: a value >= 1 is required" % (scaling["factor"],))
+    if kind == "linear":
+        return RopeSpec(th, "linear", factor, None, None, None, None)
+    lo, hi, old = number("low_freq_factor"), number("high_freq_factor"), number("original_max_position_embeddings")
+    if not (old > 0 and lo > 0 and hi > lo):
+        raise ValueError("rope scaling llama3: original_max_position_embeddings > 0 and 0 < low_freq_factor < high_freq_factor are required")
+    return RopeSpec(th, "llama3", factor, lo, hi, int(old) if old == int(old) else old, None)
+
+
+ROPE_DEFAULT = rope_spec()      # rope_theta 10000, no scaling: the table every decoder had before specs
+
+
+def rope_inv_freq(spec, dim, device=None):
+    """The inverse frequencies of a RopeSpec for head size `dim`, fp32 [dim / 2], computed on `device` with the torch operations -- and in the
+    order -- of the current transformers definitions (modeling_rope_utils): 1 / theta^(2i / dim); "linear": that divided by factor;
+    "llama3": wavelengths above original / low_freq_factor divided by factor, those below original / high_freq_factor kept, the band
+    between interpolated.  A caller-supplied inv_freq is returned as given; a length other than dim / 2 is a ValueError."""
+    if not isinstance(spec, RopeSpec):
+        raise ValueError("%r: a rope_spec() record is required" % (spec,))
+    if spec.kind == "inv_freq":
+        if len(spec.inv_freq) != dim // 2:
+            raise ValueError("inv_freq holds %d values where head_dim / 2 = %d are required" % (len(spec.inv_freq), dim // 2))
+        return torch.tensor(spec.inv_freq, dtype=torch.float32, device=device)
+    inv = 1.0 / (spec.theta ** (torch.arange(0, dim, 2, device=device, dtype=torch.float32) / dim))
+    if spec.kind == "linear":
+        inv /= spec.factor
+    elif spec.kind == "llama3":
+        factor, lo, hi, old = spec.factor, spec.low_freq_factor, spec.high_freq_factor, spec.original_max_position_embeddings
+        low_wavelen, high_wavelen = old / lo, old / hi
+        wavelen = 2 * math.pi / inv
+        scaled = torch.where(wavelen > low_wavelen, inv / factor, inv)
+        smooth = (old / wavelen - lo) / (hi - lo)
+        smoothed = (1 - smooth) * scaled / factor + smooth * scaled
+        medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+        inv = torch.where(medium, smoothed, scaled)
+    return inv
+
+
+def rope_tables(length, dim, device, dtype, spec=ROPE_DEFAULT):
+    """(cos, sin) [length, dim] in `dtype` for a RopeSpec: the angle of (position, i) is the fp32 product position * inv_freq[i] (HF's matmul of
+    the two), the rotate-half sign is folded into sin, then both are cast.  A position is a cache row."""
+    inv = rope_inv_freq(spec, dim, device)
     ang = torch.outer(torch.arange(length, device=device, dtype=torch.float32), inv)
     ang = torch.cat([ang, ang], dim=-1)
     d = dim // 2
@@ -379,8 +478,12 @@ def _rope_tables(length, dim, device, dtype, base=10000.0):
     return ang.cos().to(dtype), sin.to(dtype)
 
 
+def _rope_tables(length, dim, device, dtype, base=10000.0):
+    return rope_tables(length, dim, device, dtype, rope_spec(base))
+
+
 def _rope(x, cos, sin):
-    # x [T, H, S, D]; cos / sin [S, D]
+    # x [T, H, S, D]; cos / sin [S, D], or per tenant [T, 1, S, D]
     d = x.shape[-1] // 2
     rot = torch.cat([x[..., d:], x[..., :d]], dim=-1)
     return torch.addcmul(x * cos, rot, sin)
@@ -393,8 +496,25 @@ class TenantDecoder(nn.Module):
     MIN_STOP_WIDTH = 8          # stop ids per tenant the static stop table holds before it has to grow (to the next power of two)
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
-    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False):
+    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None):
+        """rope: the rotary embedding (rope_spec).  None: rope_theta 10000, unscaled, one [max_len, head_dim] table pair for every tenant.  One
+        spec: one shared pair built from it (a base with another rope_theta; same launches).  A list of `tenants` specs: a pair per tenant,
+        cos / sin [tenants, max_len, head_dim] -- a fine-tune's RoPE scaling is part of the fine-tune -- which load_tenant(rope=) rewrites
+        row by row."""
         super().__init__()
+        hd_ = cfg[0] // cfg[3]
+        self.rope_per_tenant = rope is not None and not isinstance(rope, RopeSpec)
+        if self.rope_per_tenant:
+            specs = list(rope)
+            if len(specs) != tenants:
+                raise ValueError("%d rope specs for %d tenants" % (len(specs), tenants))
+            self._rope_default = ROPE_DEFAULT           # what load_tenant(rope=None) gives a slot
+        else:
+            self._rope_default = ROPE_DEFAULT if rope is None else rope
+            specs = [self._rope_default] * tenants
+        for sp in specs:
+            rope_inv_freq(sp, hd_)                      # (refuses a record that is no spec, or frequencies of another head size)
+        self._rope = specs                              # slot -> its spec (tenant_rope)
         self.base_gptq4 = bool(base_gptq4)  # ... or a 4-bit GPTQ base (FusedDeltaLinear(base_gptq4=True)); lm_head, embeddings and norms stay 16-bit
         self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
         self.cfg, self.T, self.dtype, self.dev, self.eps = cfg, tenants, dtype, torch.device(device), eps
@@ -405,7 +525,11 @@ class TenantDecoder(nn.Module):
         self.embed = None           # [T, vocab, hid]
         self.final_norm = None      # [T, hid]
         self.lm_head = None         # [T, vocab, hid]
-        cos, sin = _rope_tables(max_len, self.hd, self.dev, dtype)
+        if self.rope_per_tenant:
+            pairs = [rope_tables(max_len, self.hd, self.dev, dtype, sp) for sp in specs]
+            cos, sin = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+        else:
+            cos, sin = rope_tables(max_len, self.hd, self.dev, dtype, self._rope_default)
         self.register_buffer("cos", cos, persistent=False)
         self.register_buffer("sin", sin, persistent=False)
         self._graph = None
@@ -456,14 +580,14 @@ class TenantDecoder(nn.Module):
     # ---------------------------------------------------------------- construction
     @classmethod
     def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
-                  base_gptq4=False):
+                  base_gptq4=False, rope=None):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
-        (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small)."""
+        (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope: as in __init__."""
         cfg = MODEL_CONFIGS[name] if isinstance(name, str) else tuple(name)
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
-        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4)
+        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -626,8 +750,29 @@ class TenantDecoder(nn.Module):
         Nothing in this package reads the tag yet: it is bookkeeping for a caller that keeps data per fine-tune outside the decoder."""
         return self._tags[t]
 
+    def tenant_rope(self, t):
+        """Slot t's rotary embedding (a rope_spec record): what its q and k are rotated with, at construction or since its last load_tenant"""
+        return self._rope[t]
+
+    def _load_rope(self, t, rope):
+        """the spec slot t carries after load_tenant(rope=): None is the decoder's default.  Every refusal happens here, before the first write: a
+        record that is no spec or does not fit the head size, and -- on a decoder with ONE table for all tenants -- a spec other than the
+        decoder's, which slot t could not have alone."""
+        spec = self._rope_default if rope is None else rope
+        rope_inv_freq(spec, self.hd)
+        if not self.rope_per_tenant and spec != self._rope_default:
+            raise ValueError("this decoder rotates every tenant with one table (%r): build it with a list of rope specs to give slot %d its own"
+                             % (self._rope_default, t))
+        return spec
+
+    def _rope_rows(self, pos_idx):
+        """the table rows of positions pos_idx as the stock-op attention takes them: [S, D], or per tenant [T, 1, S, D] (broadcast over the heads)"""
+        if self.cos.dim() == 3:
+            return self.cos[:, pos_idx].unsqueeze(1), self.sin[:, pos_idx].unsqueeze(1)
+        return self.cos[pos_idx], self.sin[pos_idx]
+
     @torch.no_grad()
-    def load_tenant(self, t, state, tag=None):
+    def load_tenant(self, t, state, tag=None, rope=None):
         """Replace the fine-tune in slot t IN PLACE (state: see tenant_state): every delta Linear's sign words and scales through
         FusedDeltaLinear.load_tenant, the tenant's rows of the norms, the embedding and the lm_head by copies on the current stream.  Storage and
         pointers stay, so captured decode steps stay valid and the other tenants' rows are not touched.  The one thing a captured step bakes that
@@ -641,10 +786,16 @@ class TenantDecoder(nn.Module):
         load matches it.  A hashable (say the fine-tune's name) is the CALLER's statement that equal tags mean equal weights: after A -> B -> A in
         one slot the tag is A's again, and every slot loaded with tag A compares equal.  An unhashable tag is refused (TypeError) first, and
         every refusal leaves the tag as it was.  From the first write on the slot carries a fresh unique object, and the caller's tag is
-        assigned after the last: a load that fails midway never leaves a tag that matches anything on partly new weights."""
+        assigned after the last: a load that fails midway never leaves a tag that matches anything on partly new weights.
+        rope: the slot's rotary embedding afterwards (rope_spec; tenant_rope); None, the default, is the decoder's default spec -- a load defines
+        the whole slot, positional encoding included.  On a decoder with per-tenant tables the rows cos[t] / sin[t] are rebuilt on the device
+        and copied in place on the current stream (no host read; storage, pointers and captured graphs stay valid).  On a decoder with one
+        shared table a spec other than the decoder's is refused (ValueError) before the first write.  Keys of slot t that are still in a
+        cache were rotated with the old table: they are not reusable (TenantSession.load_tenant forgets them)."""
         if tag is not None:
             hash(tag)
         self._check_state(t, state)
+        spec = self._load_rope(t, rope)
         require_gpu(self.embed)
         assert not torch.cuda.is_current_stream_capturing(), "a load reads the hand-off scale on the host: not inside a graph capture"
         peaks = self._hn_peaks(t, state)                   # the load's one host read (none without a cached hand-off norm)
@@ -659,6 +810,11 @@ class TenantDecoder(nn.Module):
                     rescaled |= self._reload_hn(layer, which, t, peaks[(li, which)])
         for name in self._DENSE:
             getattr(self, name)[t].copy_(state[name])
+        if spec != self._rope[t]:                          # (per-tenant tables only: _load_rope refused anything else)
+            cos, sin = rope_tables(self.cos.shape[-2], self.hd, self.dev, self.dtype, spec)
+            self.cos[t].copy_(cos)
+            self.sin[t].copy_(sin)
+            self._rope[t] = spec
         # The decoder's own one-tenant view is dropped and rebuilt on its next use.  That is enough: a view slices this storage and caches nothing
         # derived from tenant data (it only prefills, where no hand-off norm is made), so a view a caller still holds reads the new fine-tune too.
         self._tenant_views.pop(t, None)
@@ -745,7 +901,7 @@ class TenantDecoder(nn.Module):
         else:
             q, k, v = layer.qkv.split(qkv)
             if cos is None:                                                     # (forward() skips the gather when it expects the HIP attention)
-                cos, sin = self.cos[pos_idx], self.sin[pos_idx]
+                cos, sin = self._rope_rows(pos_idx)
             q = _rope(q.view(T, S, heads, hd).transpose(1, 2), cos, sin)
             k = _rope(k.view(T, S, kvh, hd).transpose(1, 2), cos, sin)
             v = v.view(T, S, kvh, hd).transpose(1, 2)
@@ -811,7 +967,7 @@ class TenantDecoder(nn.Module):
         hip_attn = self.fast_glue and ((S == 1 and ops.decode_attention_supported(heads, kvh, self.hd)) or
                                        (S > 1 and cache.get("kv_start") is not None and self.hd == 128 and S % 64 == 0) or
                                        (cache.get("chunk") is not None and self.hip_prefill_attention and self.hd == 128))
-        cos, sin = (None, None) if (hip_attn or ragged is not None) else (self.cos[pos_idx], self.sin[pos_idx])
+        cos, sin = (None, None) if (hip_attn or ragged is not None) else self._rope_rows(pos_idx)
         if x is None:
             t_idx = torch.arange(T, device=ids.device).view(T, 1)
             x = self.embed[t_idx, ids]                                        # per-tenant embedding: one gather
@@ -1057,8 +1213,10 @@ class TenantDecoder(nn.Module):
         views = self._tenant_views
         v = views.get(t)
         if v is None:
-            v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4)
-            v.cos, v.sin = self.cos, self.sin
+            v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4,
+                              rope=self._rope[t])
+            # the parent's table, or the tenant's rows of it: a slice of the storage load_tenant(rope=) rewrites in place
+            v.cos, v.sin = (self.cos[t], self.sin[t]) if self.rope_per_tenant else (self.cos, self.sin)
             for layer in self.layers:
                 lv = nn.Module()
                 for name in ("qkv", "o", "gate_up", "down"):
@@ -1563,19 +1721,22 @@ class TenantSession:
 
     # ------------------------------------------------------------ admission
     @torch.no_grad()
-    def load_tenant(self, t, state, tag=None):
+    def load_tenant(self, t, state, tag=None, rope=None):
         """Put another fine-tune into slot t (TenantDecoder.load_tenant) while the other tenants keep generating: refused (RuntimeError) while
         tenant t is active.  Runs on the current stream, i.e. ordered between the replays around it; tenant t's validity bytes, stop reason, token
         count and output row are cleared, nobody else's state, cache rows or validity bytes are touched.  Host reads: tenant t's own activity
         flag (as in submit) and, where a hand-off norm is cached, the decoder's one read of the new norm rows' maxima.
-        tag: the slot's fine-tune tag afterwards (TenantDecoder.load_tenant, tenant_tag); a refused load leaves the tag as it was."""
+        tag: the slot's fine-tune tag afterwards (TenantDecoder.load_tenant, tenant_tag); a refused load leaves the tag as it was.
+        rope: the slot's rotary embedding afterwards (rope_spec; None = the decoder's default), as TenantDecoder.load_tenant takes it: on per-tenant
+        tables the slot's rows are rewritten in place, so the session's captured graphs stay; a shared-table decoder refuses another spec before
+        anything is written.  The slot's cached keys were rotated with the old table: extend() after a load refuses, as before."""
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
         if tag is not None:
             hash(tag)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
-        rescaled = self.dec.load_tenant(t, state, tag=tag)
+        rescaled = self.dec.load_tenant(t, state, tag=tag, rope=rope)
         self._kv_start[t] = None                      # the cache rows belong to the fine-tune that left: nothing to extend
         self.cache["valid"][t].zero_()
         self.done[t] = 0

@@ -68,12 +68,27 @@ def swiglu_interleaved8(gu):
     return y
 
 
+def table_stride(cos, sin, tenants):
+    """The tenant stride (elements) of a pair of rotary tables as the *_tab entries take it: 0 for one shared [Lmax, 128] pair, Lmax * 128 for a
+    contiguous per-tenant [T, Lmax, 128] pair (serving_loop.rope_tables per tenant, stacked).  A per-tenant pair whose leading dimension is
+    not the launch's tenant count is a ValueError: tenant t would rotate with another tenant's rows, or read past the end.  Host only."""
+    if cos.dim() not in (2, 3) or cos.shape != sin.shape:
+        raise ValueError("rotary tables: cos %s and sin %s where [Lmax, 128] or [T, Lmax, 128] pairs are taken" % (tuple(cos.shape), tuple(sin.shape)))
+    if cos.dim() == 2:
+        return 0
+    if cos.shape[0] != tenants:
+        raise ValueError("rotary tables for %d tenants in a launch of %d" % (cos.shape[0], tenants))
+    return cos.shape[1] * cos.shape[2]
+
+
 def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads):
-    """One new token per tenant.  qkv [T, 1, (heads + 2 kv_heads) * 128]; cos / sin [Lmax, 128]; caches [T, kv_heads, Lc, 128];
+    """One new token per tenant.  qkv [T, 1, (heads + 2 kv_heads) * 128]; cos / sin [Lmax, 128], or contiguous [T, Lmax, 128]: tenant t's own
+    tables (bd_srv_decode_attention_tab); caches [T, kv_heads, Lc, 128];
     valid [T, Lc] bool; pos: int64 device tensor with one element.  Returns [T, 1, heads * 128]; the caches and valid[:, pos] are
     updated in place."""
-    require_gpu(qkv, cos, sin, kcache, vcache, valid, pos)
     T = qkv.shape[0]
+    s_tab = table_stride(cos, sin, T)
+    require_gpu(qkv, cos, sin, kcache, vcache, valid, pos)
     hd = kcache.shape[3]
     assert qkv.shape[1] == 1 and qkv.shape[2] == (heads + 2 * kv_heads) * hd and qkv.stride(2) == 1
     assert kcache.is_contiguous() and vcache.is_contiguous() and valid.is_contiguous() and valid.dtype == torch.bool
@@ -84,6 +99,11 @@ def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads)
     # persistent per-stream scratch, zero-filled once: the kernel's arrival counters must be zero at launch and it restores them
     ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)
     with torch.cuda.device(qkv.device):
+        if cos.dim() == 3:
+            check(L.bd_srv_decode_attention_tab(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(out),
+                                                T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
+                                                DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()), "srv_decode_attention_tab")
+            return out
         check(L.bd_srv_decode_attention(ptr(qkv), ptr(cos), ptr(sin), ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(out),
                                         T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
                                         DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()), "srv_decode_attention")
@@ -93,9 +113,10 @@ def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads)
 def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, heads, kv_heads):
     """decode_attention with one position per tenant: pos int64 [T], active bool [T] on the device.  Tenant t attends over its valid keys
     0 .. pos[t] and appends at pos[t]; a tenant that is inactive or whose position lies outside the cache gets a zero output row and its cache
-    and valid rows stay as they are."""
-    require_gpu(qkv, cos, sin, kcache, vcache, valid, pos, active)
+    and valid rows stay as they are.  cos / sin [Lmax, 128] or per tenant [T, Lmax, 128], as in decode_attention."""
     T = qkv.shape[0]
+    s_tab = table_stride(cos, sin, T)
+    require_gpu(qkv, cos, sin, kcache, vcache, valid, pos, active)
     hd = kcache.shape[3]
     assert qkv.shape[1] == 1 and qkv.shape[2] == (heads + 2 * kv_heads) * hd and qkv.stride(2) == 1
     assert kcache.is_contiguous() and vcache.is_contiguous() and valid.is_contiguous() and valid.dtype == torch.bool
@@ -106,6 +127,11 @@ def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, h
     need = L.bd_srv_decode_attention_workspace_bytes(T, heads, kv_heads, hd, kcache.shape[2])
     ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)          # (the scalar form's persistent scratch, same contract)
     with torch.cuda.device(qkv.device):
+        if cos.dim() == 3:
+            check(L.bd_srv_decode_attention_ragged_tab(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos),
+                                                       ptr(active), ptr(out), T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
+                                                       DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()), "srv_decode_attention_ragged_tab")
+            return out
         check(L.bd_srv_decode_attention_ragged(ptr(qkv), ptr(cos), ptr(sin), ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(active), ptr(out),
                                                T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
                                                DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()), "srv_decode_attention_ragged")
@@ -194,12 +220,19 @@ def decode_attention_supported(heads, kv_heads, head_dim):
 
 def rope_(x, cos, sin, heads, seq, pos0=0):
     """In-place rotary embedding of x [B, S, heads * 128] (a q / k projection output, before the head transpose); row r sits at position
-    pos0 + r % seq.  cos / sin [Lmax, 128] in x.dtype with the rotate-half sign folded into sin.  Returns x."""
+    pos0 + r % seq.  cos / sin [Lmax, 128] in x.dtype with the rotate-half sign folded into sin, or contiguous [B, Lmax, 128]: batch row b is
+    tenant b and rotates with its own tables (bd_srv_rope_tab; seq is then x.shape[1]).  Returns x."""
+    s_tab = table_stride(cos, sin, x.shape[0])
     require_gpu(x, cos, sin)
     assert x.dim() == 3 and x.shape[2] == heads * 128 and x.stride(2) == 1
     assert x.shape[0] == 1 or x.stride(0) == x.shape[1] * x.stride(1)
-    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == x.dtype and cos.shape[0] >= pos0 + seq
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == x.dtype and cos.shape[-2] >= pos0 + seq
     with torch.cuda.device(x.device):
+        if cos.dim() == 3:
+            assert seq == x.shape[1], "per-tenant tables: the tenant of row r is r // seq, so seq is the rows per tenant"
+            check(lib().bd_srv_rope_tab(ptr(x), ptr(cos), ptr(sin), s_tab, x.shape[0] * x.shape[1], heads, 128, x.stride(1), seq, pos0,
+                                        DTYPE_CODE[x.dtype], stream_ptr()), "srv_rope_tab")
+            return x
         check(lib().bd_srv_rope(ptr(x), ptr(cos), ptr(sin), x.shape[0] * x.shape[1], heads, 128, x.stride(1), seq, pos0,
                                 DTYPE_CODE[x.dtype], stream_ptr()), "srv_rope")
     return x
@@ -649,15 +682,21 @@ def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cac
 def rope_kv_append_(qkv, cos, sin, kcache, vcache, heads, kvh, pos0=0):
     """Prefill from position pos0: rope_ on the q and k heads of the fused projection output qkv [T, S, (heads + 2 kvh) * 128] (in place) and, in the
     same launch, the rotated k rows and the v rows into the caches [T, kvh, Lc, 128] at positions pos0 .. pos0 + S - 1 (what
-    `kcache[:, :, pos0:pos0 + S] = k.transpose(1, 2)` and its v twin do after rope_).  Returns qkv."""
-    require_gpu(qkv, cos, sin, kcache, vcache)
+    `kcache[:, :, pos0:pos0 + S] = k.transpose(1, 2)` and its v twin do after rope_).  cos / sin [Lmax, 128], or contiguous [T, Lmax, 128]: tenant
+    t's own tables (bd_srv_rope_kv_append_tab).  Returns qkv."""
     T, S, W = qkv.shape
+    s_tab = table_stride(cos, sin, T)
+    require_gpu(qkv, cos, sin, kcache, vcache)
     assert W == (heads + 2 * kvh) * 128 and qkv.stride(2) == 1 and (T == 1 or qkv.stride(0) == S * qkv.stride(1))
-    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == qkv.dtype and cos.shape[0] >= pos0 + S
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == qkv.dtype and cos.shape[-2] >= pos0 + S
     Lc = kcache.shape[2]
     assert kcache.shape == (T, kvh, Lc, 128) and vcache.shape == kcache.shape and kcache.is_contiguous() and vcache.is_contiguous()
     assert kcache.dtype == qkv.dtype and vcache.dtype == qkv.dtype and pos0 + S <= Lc
     with torch.cuda.device(qkv.device):
+        if cos.dim() == 3:
+            check(lib().bd_srv_rope_kv_append_tab(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), T, S, heads, kvh, 128, qkv.stride(1),
+                                                  Lc, pos0, DTYPE_CODE[qkv.dtype], stream_ptr()), "srv_rope_kv_append_tab")
+            return qkv
         check(lib().bd_srv_rope_kv_append(ptr(qkv), ptr(cos), ptr(sin), ptr(kcache), ptr(vcache), T, S, heads, kvh, 128, qkv.stride(1), Lc, pos0,
                                           DTYPE_CODE[qkv.dtype], stream_ptr()), "srv_rope_kv_append")
     return qkv

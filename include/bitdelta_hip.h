@@ -262,6 +262,16 @@ int bd_srv_rope(void* X, const void* cos_t, const void* sin_t, int rows, int hea
  * the HF attention module the reference's Linears sit in; demo/demo_backend.py:297-315 prefills through it).  pos0 + S <= Lc. */
 int bd_srv_rope_kv_append(void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, int T, int S, int H, int KVH,
                           int head_dim, int64_t sx, int Lc, int pos0, int dtype, void* stream);
+/* bd_srv_rope_tab / bd_srv_rope_kv_append_tab: the two entries above with PER-TENANT rotary tables (a fine-tune with its own rope_theta or RoPE
+ * scaling; serving_loop.rope_spec).  s_tab is the tenant stride of cos_t / sin_t in elements: 0 = one shared [Lmax, 128] table (then the same
+ * launch and the same bits as the entry without the argument, which is this one at s_tab = 0); otherwise the tables are [T, Lmax, 128] and
+ * tenant t's rows start at cos_t + t * s_tab.  bd_srv_rope_tab: the tenant of row r is r / seq (X is [T * seq, heads*128]).  Everything else,
+ * NULL handling included, as in the originals.  BD_E_BAD_SHAPE, before any device call, when s_tab < 0 or s_tab % 8 != 0 (every tenant's rows stay
+ * 16-byte aligned: the kernels read the tables in 16-byte chunks) or a table pointer is not 16-byte aligned. */
+int bd_srv_rope_tab(void* X, const void* cos_t, const void* sin_t, int64_t s_tab, int rows, int heads, int head_dim, int64_t sx, int seq, int pos0,
+                    int dtype, void* stream);
+int bd_srv_rope_kv_append_tab(void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, int T, int S, int H,
+                              int KVH, int head_dim, int64_t sx, int Lc, int pos0, int dtype, void* stream);
 /* bd_srv_step_begin / bd_srv_step_end (round 6): the two ends of ONE greedy decode step of the serving loop (demo/demo_backend.py:190-258: HF's
  * generate loop over the tenant batch -- embedding lookup of the last tokens, attention-mask extension, argmax of the last logits, stop-token check).
  * step_begin: X[t] = embed[t][tok[t]] (embed [T, V, H] 16-bit, tenant stride sEt -- 0 = one shared table -- row stride sEv; X [T, H], row stride sx)
@@ -582,6 +592,19 @@ int bd_srv_decode_attention(const void* QKV, const void* cos_t, const void* sin_
 int bd_srv_decode_attention_ragged(const void* QKV, const void* cos_t, const void* sin_t, void* kcache, void* vcache, void* valid,
                                    const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
                                    int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
+/* bd_srv_decode_attention_tab / bd_srv_decode_attention_ragged_tab: the two entries above with PER-TENANT rotary tables.  s_tab is the tenant
+ *   stride of cos_t / sin_t in elements: 0 = one shared [Lmax, 128] table (the same launch and the same bits as the entry without the argument);
+ *   otherwise [T, Lmax, 128] with tenant t's rows at cos_t + t * s_tab, so tenant t's q and new k are rotated with row pos (ragged: pos[t]) of ITS
+ *   table.  The same kernels: the stride is a launch argument, the tenant's offset is scalar arithmetic in front of the RoPE inputs' loads.
+ *   Validation, workspace, split rule, ring depth, NULL handling and the ragged form's stay-out rule as in the originals.  BD_E_BAD_SHAPE, before any
+ *   device call, when s_tab < 0, s_tab % 8 != 0 or a table pointer is not 16-byte aligned (the entries without the argument do not ask for
+ *   aligned tables and keep not asking). */
+int bd_srv_decode_attention_tab(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, void* valid,
+                                const int64_t* pos, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
+int bd_srv_decode_attention_ragged_tab(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, void* valid,
+                                       const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                       int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
 /* bd_srv_prefill_attention: attention of a whole prompt (the prefill call of the serving loop, demo/demo_backend.py:262-275 -> the HF
  *   decoder layer's attention with the left-padded attention_mask; what F.scaled_dot_product_attention computes there), flash-style:
  *   O[b, s, h] = softmax_k(Q[b, s, h] . K[b, k, h / (H/KVH)] * scale) . V[b, k, h / (H/KVH)] over the keys kv_start[b] <= k (<= s when
