@@ -70,6 +70,8 @@ SIGNATURES = {
     "bd_srv_ban_rows": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _ci, _vp, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _vp]),
     "bd_srv_step_ban": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _ci, _vp, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci,
                               _vp]),
+    "bd_srv_truncate_rows": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _vp, _ci, _ci, _vp]),
+    "bd_srv_step_truncate": (_ci, [_vp, _i64, _ci, _vp, _i64, _vp, _vp, _vp, _ci, _ci, _vp]),
     "bd_srv_rope_kv_append": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_rope": (_ci, [_vp, _vp, _vp, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_decode_attention": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64, _vp]),

@@ -29,6 +29,7 @@
 #include "bd_constrain.h"
 #include "bd_stop_seq.h"
 #include "bd_ban.h"
+#include "bd_truncate.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2399,4 +2400,39 @@ extern "C" int bd_srv_step_ban(const void* logits, int64_t sl, int V, void* out,
                                int ns, const uint8_t* active, int T, int dtype, void* stream) {
     return ban_launch(logits, sl, V, out, so, ctx, Lc, ctx_len, toks, s_tok, tok_cap, n, ban_ngram, ban_tok, ban_len, Q, W, ban_min, stop_ids, ns,
                       active, T, dtype, true, stream);
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// One body for the two truncation entry points: step == false is bd_srv_truncate_rows (R live rows), true bd_srv_step_truncate (T tenants).
+static int truncate_launch(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params,
+                           const uint8_t* active, int R, int dtype, bool step, void* stream) {
+    if (R < 0 || V < 1 || V > NLL_V_MAX) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (R == 0) return BD_OK;
+    if (!logits || !out || !tau || !params || (step && !active)) return BD_E_NULL;
+    if (V % 8 || sl % 8 || so % 8 || sl < V || so < V || !aligned16(logits) || !aligned16(out) || !aligned_to(tau, 4) || !aligned_to(params, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    // the form depends on V alone, as in bd_srv_token_nll: <= 8192 / <= 32768 hold the row in 4 / 16 sixteen-byte registers per thread
+#define BD_TRUNC_LAUNCH(DT, NV)                                                                                                            \
+    hipLaunchKernelGGL((truncate_kernel<DT, NV>), dim3((unsigned)R), dim3(256), 0, st, (const unsigned short*)logits, (long long)sl, V,    \
+                       (unsigned short*)out, (long long)so, tau, params, (const unsigned char*)(step ? active : nullptr))
+    const int nv = V <= 2048 * 4 ? 4 : V <= 2048 * NLL_NV_MAX ? NLL_NV_MAX : 0;
+    if (dtype == BD_BF16) {
+        if (nv == 4) BD_TRUNC_LAUNCH(DT_BF16, 4); else if (nv == NLL_NV_MAX) BD_TRUNC_LAUNCH(DT_BF16, NLL_NV_MAX); else BD_TRUNC_LAUNCH(DT_BF16, 0);
+    } else {
+        if (nv == 4) BD_TRUNC_LAUNCH(DT_F16, 4); else if (nv == NLL_NV_MAX) BD_TRUNC_LAUNCH(DT_F16, NLL_NV_MAX); else BD_TRUNC_LAUNCH(DT_F16, 0);
+    }
+#undef BD_TRUNC_LAUNCH
+    return launch_status();
+}
+
+extern "C" int bd_srv_truncate_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params, int R,
+                                    int dtype, void* stream) {
+    return truncate_launch(logits, sl, V, out, so, tau, params, nullptr, R, dtype, false, stream);
+}
+
+extern "C" int bd_srv_step_truncate(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params,
+                                    const uint8_t* active, int T, int dtype, void* stream) {
+    return truncate_launch(logits, sl, V, out, so, tau, params, active, T, dtype, true, stream);
 }

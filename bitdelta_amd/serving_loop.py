@@ -1235,7 +1235,7 @@ class TenantDecoder(nn.Module):
 
     def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
                 max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8, bans=False, max_bad_words=16,
-                max_bad_word_len=8):
+                max_bad_word_len=8, truncation=False):
         """A TenantSession on this decoder's KV cache: per-tenant admission and retirement around the same decode step.  sampling=True: every
         request carries its own temperature / top_k / top_p / seed (TenantSession); the default session is greedy and takes none of them.
         logprobs=k (0 .. 20): the session also keeps every emitted token's log-probability and its k most probable alternatives
@@ -1252,11 +1252,14 @@ class TenantDecoder(nn.Module):
         before.
         bans=True: every request may also carry no_repeat_ngram_size= / bad_words= / min_new_tokens= (ban_params; at most max_bad_words <= 64
         sequences of at most max_bad_word_len <= 32 ids each): tokens its own history forbids are never chosen; independent of the other
-        five.  The default session refuses them, allocates nothing for them and runs the step it ran before."""
+        five.  The default session refuses them, allocates nothing for them and runs the step it ran before.
+        truncation=True (needs sampling=True, ValueError otherwise): every request may also carry min_p= / typical_p= / epsilon_cutoff= /
+        eta_cutoff= (truncation_params): the tail of its distribution is cut by the row's own statistics before top-k / top-p.  The default
+        session refuses them, allocates nothing for them and runs the step it ran before."""
         return TenantSession(self, max_stop_ids, sampling=sampling, logprobs=logprobs, penalties=penalties, max_logit_bias=max_logit_bias,
                              constraints=constraints, max_constraint_states=max_constraint_states, max_constraint_edges=max_constraint_edges,
                              stop_sequences=stop_sequences, max_stop_sequences=max_stop_sequences, max_stop_sequence_len=max_stop_sequence_len,
-                             bans=bans, max_bad_words=max_bad_words, max_bad_word_len=max_bad_word_len)
+                             bans=bans, max_bad_words=max_bad_words, max_bad_word_len=max_bad_word_len, truncation=truncation)
 
     def _graph_runner(self, st):
         """Capture one decode step as a hipGraph on the request's static buffers and return a replay callable.  The launch-bound
@@ -1537,6 +1540,38 @@ def ban_word_table(words, Q, W):
     return [list(w) + [-1] * (W - len(w)) for w in words] + [[-1] * W for _ in range(pad)], [len(w) for w in words] + [0] * pad
 
 
+def truncation_params(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """The tail truncation of one request, validated on the host: (min_p, typical_p, epsilon_cutoff, eta_cutoff) as four floats -- the canonical
+    form: two requests that mean the same compare equal.  include/bitdelta_hip.h (bd_srv_truncate_rows) defines what they drop.  min_p in
+    [0, 1] (0 = off; HF's MinPLogitsWarper); typical_p in (0, 1] (1 = off; TypicalLogitsWarper); epsilon_cutoff in [0, 1) (0 = off;
+    EpsilonLogitsWarper); eta_cutoff in [0, 1) (0 = off; EtaLogitsWarper).  Anything else -- a value outside its range, a NaN, an infinity, a
+    bool or something that is no number -- raises ValueError.  The defaults drop nothing (NO_TRUNCATION)."""
+    def number(v, what):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            x = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s = %r: a number is required" % (what, v))
+        if not math.isfinite(x):
+            raise ValueError("%s = %r: a finite value is required" % (what, v))
+        return x + 0.0                                 # (-0.0 -> 0.0: one canonical zero)
+    mp, ty = number(min_p, "min_p"), number(typical_p, "typical_p")
+    ep, et = number(epsilon_cutoff, "epsilon_cutoff"), number(eta_cutoff, "eta_cutoff")
+    if not (0.0 <= mp <= 1.0):
+        raise ValueError("min_p = %r: 0 <= min_p <= 1 is required (0 = off)" % (min_p,))
+    if not (0.0 < ty <= 1.0):
+        raise ValueError("typical_p = %r: 0 < typical_p <= 1 is required (1 = off)" % (typical_p,))
+    if not (0.0 <= ep < 1.0):
+        raise ValueError("epsilon_cutoff = %r: 0 <= epsilon_cutoff < 1 is required (0 = off)" % (epsilon_cutoff,))
+    if not (0.0 <= et < 1.0):
+        raise ValueError("eta_cutoff = %r: 0 <= eta_cutoff < 1 is required (0 = off)" % (eta_cutoff,))
+    return mp, ty, ep, et
+
+
+NO_TRUNCATION = truncation_params()
+
+
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
     own max_new_tokens or the end of its cache rows, while the other tenants keep generating.  The decode step is the decoder's -- the same
@@ -1612,6 +1647,20 @@ class TenantSession:
     the RAW logits' distribution.  Without bans=True the session refuses non-default values (ValueError), allocates none of this and launches
     nothing more.
 
+    truncation=True (a sampling session only): a request may carry min_p= / typical_p= / epsilon_cutoff= / eta_cutoff= (truncation_params;
+    include/bitdelta_hip.h, bd_srv_truncate_rows, defines the kept set) -- Hugging Face's MinPLogitsWarper, TypicalLogitsWarper,
+    EpsilonLogitsWarper and EtaLogitsWarper, the filters that cut the tail by the row's own statistics at the request's temperature.  The
+    session keeps the four numbers per tenant (trunc [T, 4] float32, written at admission) and ONE more launch (serving_ops.step_truncate)
+    sits behind step_penalize, step_constrain and step_ban -- the last of the masks, judged on the row they leave -- and in front of
+    step_end_sample, which reads its output tlogits [T, V], applies top-k / top-p to the survivors and draws.  With one filter set and top-k /
+    top-p off this is the Hugging Face warper of that name; with several set the kept set is the INTERSECTION of the sets each filter keeps on
+    the same row (HF applies them one after another on renormalised survivors), and typical_p is ignored on a row where its set does not meet
+    the thresholds' set.  typical_p may drop the most probable token.  A greedy request (temperature 0) is not touched.  The launch keeps no
+    counter: it is a pure function of the row and the five numbers.  The first token is chosen from serving_ops.truncate_rows of the
+    (penalised, constrained, banned) prefill logits.  Nothing is baked into the captured graph.  result_logprobs keeps reporting the RAW
+    logits' distribution.  Without truncation=True the session refuses non-neutral values (ValueError), allocates none of this and launches
+    nothing more.
+
     One sequence per tenant, the decoder's ONE KV cache.  `generate` is the lockstep loop of the reference and is not changed by this:
     it runs every tenant until all have stopped, a session stops each tenant at ITS stop token.
     reason (result(t)[1], bits): 1 = stop token, 2 = max_new_tokens reached, 4 = the cache is full, 8 = the constraint is complete (a final state
@@ -1619,8 +1668,11 @@ class TenantSession:
 
     def __init__(self, dec, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
                  max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8,
-                 bans=False, max_bad_words=16, max_bad_word_len=8):
+                 bans=False, max_bad_words=16, max_bad_word_len=8, truncation=False):
         self.logprobs = logprobs_count(logprobs)
+        self.truncation = bool(truncation)
+        if self.truncation and not sampling:
+            raise ValueError("truncation=True cuts the tail of a sampled distribution: make the session with sampling=True as well")
         self.penalties = bool(penalties)
         self.constraints = bool(constraints)
         self.stop_sequences = bool(stop_sequences)
@@ -1714,6 +1766,9 @@ class TenantSession:
             self.ban_min = torch.zeros(T, dtype=torch.int32, device=dev)
             self.blogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
             self._ctx_tokens = [[] for _ in range(T)]  # the host's copy of ctx[t, :ctx_len[t]]: extend appends to it
+        if self.truncation:                           # per tenant: (min_p, typical_p, epsilon_cutoff, eta_cutoff), and the truncated row
+            self.trunc = torch.tensor([NO_TRUNCATION] * T, dtype=torch.float32).to(dev)
+            self.tlogits = torch.zeros(T, dec.lm_head.shape[-2], dtype=dec.lm_head.dtype, device=dev)
         self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
         self._graphs = {}
         self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
@@ -1756,6 +1811,8 @@ class TenantSession:
             self._write_stop_sequences(t, self._stop_sequences_arg(()), -1, 0, 0)
         if self.bans:
             self._write_bans(t, NO_BANS, [], [])
+        if self.truncation:
+            self._write_truncation(t, NO_TRUNCATION)
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -1805,6 +1862,19 @@ class TenantSession:
             return bp
         return ban_params(no_repeat_ngram_size, bad_words, min_new_tokens, vocab=self.dec.lm_head.shape[-2], max_bad_words=self.ban_tok.shape[1],
                           max_bad_word_len=self.ban_tok.shape[2])
+
+    def _truncation_params(self, min_p, typical_p, epsilon_cutoff, eta_cutoff):
+        """one request's validated truncation, before anything is touched; a session made without truncation=True takes the neutral values only"""
+        tp = truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        if not self.truncation and tp != NO_TRUNCATION:
+            raise ValueError("this session truncates nothing: make it with session(sampling=True, truncation=True) to pass min_p / typical_p / "
+                             "epsilon_cutoff / eta_cutoff")
+        return tp
+
+    def _write_truncation(self, t, tp):
+        """a truncation session, before the first token is chosen: tenant t's four numbers.  One torch op on the current stream, no host read."""
+        if self.truncation:
+            self.trunc[t] = torch.tensor(tp, dtype=torch.float32).to(self.dec.dev)
 
     def _per_tenant_bad_words(self, v):
         """submit_all's bad_words=: one list of token-id lists for all tenants, or a list with one such list per tenant, told apart by depth as
@@ -1952,6 +2022,8 @@ class TenantSession:
             self._keep_first_logprobs(raw, tok)
             return tok.tolist()
         dev = self.dec.dev
+        if self.truncation:                           # the last of the masks, at the request's own temperature (_admit writes it to the device later)
+            logits = ops.truncate_rows(logits, torch.tensor([sp[0] for sp in sps], dtype=torch.float32).to(dev), self.trunc[rows].contiguous())
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
             logits = logits.contiguous()
         tok = ops.sample_rows(logits, torch.tensor([sp[0] for sp in sps], dtype=torch.float32).to(dev),
@@ -2012,7 +2084,7 @@ class TenantSession:
     @torch.no_grad()
     def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
                presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
-               bad_words=(), min_new_tokens=0):
+               bad_words=(), min_new_tokens=0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """Admit one request for tenant t; the other tenants' state, cache rows and validity bytes are not touched.  The prompt is left-padded to
         padded_length(len(prompt)) and refused beyond MAX_PROMPT (the reference's per-request rules, per tenant), prefilled for this tenant
         alone through tenant_view(t), and the tenant starts at its own position.  temperature / top_k / top_p / seed: sampling_params, in a
@@ -2023,7 +2095,9 @@ class TenantSession:
         stop_sequences: a list of token-id lists, in a session(stop_sequences=True): the tenant retires with reason 16 in the step after which
         this turn's tokens end with one of them (stop_sequence_table's refusals: ValueError, before anything is touched).
         no_repeat_ngram_size / bad_words / min_new_tokens: ban_params, in a session(bans=True); the history they look at is the prompt's real
-        tokens followed by the turn's own, and the first token obeys them too."""
+        tokens followed by the turn's own, and the first token obeys them too.
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: truncation_params, in a session(sampling=True, truncation=True); they cut the row the
+        token is sampled from, behind every other mask and in front of top-k / top-p, and the first token obeys them too."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
         sp = self._params(temperature, top_k, top_p, seed)
@@ -2031,6 +2105,7 @@ class TenantSession:
         con = self._constraint_arg(constraint)
         ss = self._stop_sequences_arg(stop_sequences)
         bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
+        tp = self._truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
         self._check_tokens(prompt)
         self._check_conversation(prompt)
         if bool(self.active_flags[t]):
@@ -2050,13 +2125,14 @@ class TenantSession:
         self._context(t, prompt, pp)
         self._write_constraint(t, con, stops)
         self._write_bans(t, bp, prompt, stops)
+        self._write_truncation(t, tp)
         self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con, ss=ss)
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
     def extend(self, t, tokens, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
                presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
-               bad_words=(), min_new_tokens=0):
+               bad_words=(), min_new_tokens=0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """The next turn of tenant t's conversation FROM ITS CACHED KEYS: `tokens` (the new user turn; may be empty) follow what the tenant was
         submitted and has generated so far, and only they are prefilled -- the reference re-sends and re-prefills the whole history with every
         request (demo/demo_backend.py:261-315).  The cache of a retired tenant holds its conversation up to, not including, its last emitted
@@ -2077,7 +2153,8 @@ class TenantSession:
         no_repeat_ngram_size / bad_words / min_new_tokens as in submit (this turn's own).  The history they look at is the WHOLE conversation:
         what the tenant was submitted, every earlier turn's emitted tokens and new tokens, then `tokens`, then this turn's own -- an n-gram seen
         only in turn one is banned in turn two; min_new_tokens counts this turn's tokens.  A ban session reads the earlier turn's tokens back
-        (one more host read) to keep that history."""
+        (one more host read) to keep that history.
+        min_p / typical_p / epsilon_cutoff / eta_cutoff as in submit (this turn's own; they replace the turn before's)."""
         dec = self.dec
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
@@ -2089,6 +2166,7 @@ class TenantSession:
         con = self._check_constraint(self._constraint_arg(constraint), stops)
         ss = self._stop_sequences_arg(stop_sequences)
         bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
+        tp = self._truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
         self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
@@ -2102,22 +2180,26 @@ class TenantSession:
         self._context(t, [last] + tokens, pp, fold=True)
         self._write_constraint(t, con, stops)
         self._write_bans(t, bp, conv, stops)
+        self._write_truncation(t, tp)
         self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con, ss=ss)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
                    presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, constraint=None, stop_sequences=(), no_repeat_ngram_size=0,
-                   bad_words=(), min_new_tokens=0):
+                   bad_words=(), min_new_tokens=0, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """The reference's request shape: one prompt per tenant, one batched prepare + prefill exactly as generate does, every tenant at the
         common padded length.  temperature / top_k / top_p / seed and the four penalty arguments: each one value for all (a logit_bias mapping
         is one value) or a list with one value per tenant.  constraint: None or one TokenAutomaton for all, or a list with one (or None) per
         tenant.  stop_sequences: one list of token-id lists for all, or a list with one such list per tenant; the two are told apart by depth
         (_per_tenant_stop_sequences).  no_repeat_ngram_size / min_new_tokens: one value for all or a list with one per tenant; bad_words: one list
-        of token-id lists for all or a list with one such list per tenant, told apart as stop_sequences are."""
+        of token-id lists for all or a list with one such list per tenant, told apart as stop_sequences are.  min_p / typical_p / epsilon_cutoff /
+        eta_cutoff: each one value for all or a list with one per tenant."""
         dec = self.dec
         assert max_new_tokens >= 1
         bps = [self._ban_params(*a) for a in zip(self._per_tenant(no_repeat_ngram_size), self._per_tenant_bad_words(bad_words),
                                                  self._per_tenant(min_new_tokens))]
+        tps = [self._truncation_params(*a) for a in zip(self._per_tenant(min_p), self._per_tenant(typical_p), self._per_tenant(epsilon_cutoff),
+                                                        self._per_tenant(eta_cutoff))]
         sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
                                              self._per_tenant(seed))]
         pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
@@ -2141,6 +2223,7 @@ class TenantSession:
             self._context(t, prompts[t], pps[t])
             self._write_constraint(t, cons[t], stops[t])
             self._write_bans(t, bps[t], prompts[t], stops[t])
+            self._write_truncation(t, tps[t])
         first = self._first_tokens(logits, sps, L)
         for t in range(self.T):
             self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t], ss=sss[t])
@@ -2161,6 +2244,8 @@ class TenantSession:
         if self.bans:                                 # masks what the tenant's own history forbids; wins over a positive bias and a constraint's edge
             logits = ops.step_ban(logits, self.blogits, self.ctx, self.ctx_len, self.out, self.n, self.ban_ngram, self.ban_tok, self.ban_len,
                                   self.ban_min, self.stop_ids, self.active_flags)
+        if self.truncation:                           # the last of the masks: cuts the tail of the row the others leave, at the tenant's temperature
+            logits = ops.step_truncate(logits, self.tlogits, self.temperature, self.trunc, self.active_flags)
         if self.sampling:
             ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
                                 self.temperature, self.top_k, self.top_p, self.seed)
@@ -2191,7 +2276,8 @@ class TenantSession:
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
         and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
         one more launch in front of the last; constraints: one more in front of the last and one behind it; stop sequences: one more at the very end, on a table of the
-        session's two sizes; bans: one more in front of the step end, on a table of the session's two sizes) alone."""
+        session's two sizes; bans: one more in front of the step end, on a table of the session's two sizes; truncation: one more in front of the
+        step end) alone."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
                self.sampling, self.logprobs, self.penalties, self.constraints)
@@ -2199,6 +2285,8 @@ class TenantSession:
             key = key + (True, self.ss_tok.shape[1], self.ss_tok.shape[2])
         if self.bans:                                 # (likewise; the launch keeps no counter, so _state() gains nothing)
             key = key + ("bans", self.ban_tok.shape[1], self.ban_tok.shape[2])
+        if self.truncation:                           # (likewise)
+            key = key + ("truncation",)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:

@@ -660,6 +660,54 @@ def step_ban(logits, out, ctx, ctx_len, toks, n, ban_ngram, ban_tok, ban_len, ba
     return out
 
 
+def _truncate_args(logits, out, tau, params):
+    """the checks truncate_rows and step_truncate share; returns out"""
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and V % 8 == 0 and logits.dtype in (torch.float16, torch.bfloat16)
+    if out is None:
+        out = torch.empty((R, V), dtype=logits.dtype, device=logits.device)
+    require_gpu(out, tau, params)
+    assert out.shape == (R, V) and out.dtype == logits.dtype and out.stride(1) == 1
+    assert tau.dtype == torch.float32 and tau.is_contiguous() and tau.numel() == R
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.shape == (R, 4)
+    return out
+
+
+def truncate_rows(logits, tau, params, out=None):
+    """The copy of logits [R, V] (16-bit, V % 8 == 0) with every element -inf that the row's min_p / typical_p / epsilon_cutoff / eta_cutoff drop at
+    its temperature, every other element keeping its bits; include/bitdelta_hip.h (bd_srv_truncate_rows) is the definition.  tau float32 [R];
+    params float32 [R, 4] = (min_p, typical_p, epsilon_cutoff, eta_cutoff) per row, (0, 1, 0, 0) = nothing.  A row with neutral parameters, a
+    temperature outside (0, inf), a NaN, a +inf or nothing finite is copied bit for bit.  Rows of logits may be strided (stride % 8 == 0, 16-byte
+    aligned; logits of another layout are copied first, as in ban_rows); out: a tensor of the logits' shape and dtype to write into instead of a
+    new one (it must not overlap logits)."""
+    require_gpu(logits)
+    assert logits.dim() == 2
+    R, V = logits.shape
+    sl = logits.stride(0) if R > 1 else V
+    if logits.stride(1) != 1 or sl % 8 or sl < V or logits.data_ptr() % 16:             # (token_logprobs' rule: such rows are copied first)
+        logits, sl = logits.contiguous(), V
+    out = _truncate_args(logits, out, tau, params)
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_truncate_rows(ptr(logits), sl, V, ptr(out), out.stride(0) if R > 1 else V, ptr(tau), ptr(params), R,
+                                         DTYPE_CODE[logits.dtype], stream_ptr()), "srv_truncate_rows")
+    return out
+
+
+def step_truncate(logits, out, tau, params, active):
+    """truncate_rows inside a ragged decode step, logits [T, V] -> out [T, V], the last of the masks: behind the lm_head, step_penalize,
+    step_constrain and step_ban and in front of step_end_sample, which then reads `out`; tau is the step end's temperature array.  An inactive
+    tenant's row of out is not touched.  The launch only reads: it keeps no counter.  active [T] bool / uint8."""
+    require_gpu(logits, active)
+    assert logits.dim() == 2
+    out = _truncate_args(logits, out, tau, params)
+    T, V = logits.shape
+    assert active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == T
+    with torch.cuda.device(logits.device):
+        check(lib().bd_srv_step_truncate(ptr(logits), logits.stride(0) if T > 1 else V, V, ptr(out), out.stride(0) if T > 1 else V, ptr(tau), ptr(params), ptr(active), T,
+                                         DTYPE_CODE[logits.dtype], stream_ptr()), "srv_step_truncate")
+    return out
+
+
 def step_end_sample(logits, tok, out, n, pos, limit, stop_ids, active, done, cache_len, temperature, top_k, top_p, seed, dbg=None):
     """step_end_ragged with tenant t's token chosen by sample_rows' rule from (temperature[t], top_k[t], top_p[t], seed[t]) and the draw index
     pos[t] + 1 (the cache row the token will occupy); temperature[t] == 0 is step_end_ragged's token.  The parameters are device arrays [T]."""

@@ -574,6 +574,48 @@ int bd_srv_step_ban(const void* logits, int64_t sl, int V, void* out, int64_t so
                     const int64_t* toks, int64_t s_tok, int tok_cap, const int64_t* n, const int32_t* ban_ngram, const int32_t* ban_tok,
                     const int32_t* ban_len, int Q, int W, const int32_t* ban_min, const int64_t* stop_ids, int ns, const uint8_t* active, int T,
                     int dtype, void* stream);
+/* bd_srv_truncate_rows: the sampling filters that cut a row's tail by the row's OWN statistics -- Hugging Face's MinPLogitsWarper (min_p),
+ * TypicalLogitsWarper (typical_p), EpsilonLogitsWarper (epsilon_cutoff) and EtaLogitsWarper (eta_cutoff) -- as one masked copy of the row.
+ * Per row r: the logits l[0 .. V) (fp16 / bf16, V % 8 == 0), its temperature tau[r] (float32) and params[r, 0:4] (float32, contiguous [R, 4]):
+ *   min_p          in [0, 1]   neutral 0
+ *   typical_p      in (0, 1]   neutral 1
+ *   epsilon_cutoff in [0, 1)   neutral 0
+ *   eta_cutoff     in [0, 1)   neutral 0
+ * out[v] is l[v], the same 16 bits, for a kept element and -inf (the dtype's bit pattern) for a dropped one; an element that was -inf stays
+ * -inf.  The row is COPIED bit for bit (all V elements) when all four parameters are neutral, when tau is not in (0, inf) (a greedy request),
+ * or when the row is special -- it holds a NaN or +inf, or nothing finite -- where the step end's greedy rule decides.
+ * Statistics, over the finite elements F with maximum m: x_i = (l_i - m) / tau, w_i = exp(x_i), Z = sum w_i, p_i = w_i / Z, mu = sum p_i x_i,
+ * H = ln Z - mu (the entropy of the row's distribution at tau).
+ * Thresholds.  theta = max( ln min_p [min_p > 0], ln eps + ln Z [eps > 0], ln min(eta, sqrt(eta) exp(-H)) + ln Z [eta > 0] ), clamped to
+ * <= 0; element i passes when x_i >= theta.  Every element equal to the maximum therefore passes (HF's min_tokens_to_keep = 1).
+ * typical_p < 1.  The key is a_i = |x_i - mu| (= |-ln p_i - H|); element i passes when the mass of the elements with a strictly smaller key
+ * is below typical_p.  Ties are all kept, as with the top-k threshold.  The most typical element always passes; the maximum need not.
+ * All filters are judged on the row the launch receives (after penalties, constraints and bans, before top-k / top-p), and the kept set is the
+ * INTERSECTION of their sets; if typical_p's set does not meet the thresholds' set, typical_p is ignored for that row.  With one filter set and
+ * top-k / top-p off this is the Hugging Face warper of that name; with several, or with top-k / top-p behind it, the order is the project's
+ * own (HF applies them one after another on renormalised survivors).
+ * Arithmetic: the masses are bd_srv_sample_rows' 2^-40 fixed-point words, Z and sum w_i (-x_i) INTEGER sums of such words, ln Z, mu and theta
+ * formed once in fp64 from the integers, x in fp32, the key |x - mu| in 2^-27 fixed point (finer than x's own fp32 rounding wherever
+ * |x| > 0.06; an element that weighs anything lies below 32); the typical_p select is an exact radix select over the four bytes of that key
+ * with integer mass histograms.  A finite element whose l - m or x overflows fp32 (a bf16 row wider than FLT_MAX, a tiny tau) has x = -inf:
+ * mass 0 and the lowest key.  No floating-point atomics: out is a pure function of the row and the five numbers -- nothing depends on R, the
+ * row's index, the strides, the form (rows / step), thread order, or graph or eager execution -- and the launch keeps no counter.
+ * Device values the host could not have written are neutralised: a NaN parameter, min_p <= 0, typical_p outside (0, 1), eps <= 0 and eta <= 0
+ * are off; min_p >= 1 keeps the maximum only.  tests/truncation_ref.py restates the definition in fp64 with the tolerance the tests allow.
+ * logits / out [R, V] with row strides sl / so (elements); elements V .. stride - 1 of a row are neither read nor written; out must not overlap
+ * logits.  Checked before any device call, in this order: R < 0, V < 1, V > 2^22 -> BD_E_BAD_SHAPE; dtype not fp16 / bf16 -> BD_E_BAD_DTYPE;
+ * R == 0 -> BD_OK, nothing launched; a pointer NULL -> BD_E_NULL; V % 8, a stride % 8 or < V, logits / out not 16-byte, tau / params not
+ * 4-byte aligned -> BD_E_BAD_SHAPE.
+ * One 256-thread block per row; up to V = 32768 the row is read once and lives in registers.  A row pays for what it asks: min_p alone the
+ * maximum and the mask pass; epsilon adds Z; eta or typical_p add mu; only typical_p runs the select. */
+int bd_srv_truncate_rows(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params, int R, int dtype,
+                         void* stream);
+/* bd_srv_step_truncate: bd_srv_truncate_rows inside a ragged decode step, the last of the masks: behind the lm_head, bd_srv_step_penalize,
+ * bd_srv_step_constrain and bd_srv_step_ban (whose row it then reads) and in front of bd_srv_step_end_sample (which then reads `out`, applies
+ * top-k / top-p to it and draws); tau is the step end's temperature array, active bytes [T].  An inactive tenant's out row is not touched and
+ * nothing of it is read.  Checks as above with T for R; active NULL -> BD_E_NULL. */
+int bd_srv_step_truncate(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params,
+                         const uint8_t* active, int T, int dtype, void* stream);
 /* bd_srv_cache_warm (round 6): reads [p0, p0 + bytes0) and [p1, p1 + bytes1) (16-byte aligned; whole 16-byte chunks) and discards the values:
  * a weight-prefetch launch for a hipGraph side branch (the serving loop forks it next to the decode attention launch so that the o projection's
  * weight and sign words sit in the Infinity Cache when it starts).  blocks = 0: one 256-thread block per CU.  No reference counterpart (the
