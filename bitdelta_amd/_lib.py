@@ -83,6 +83,11 @@ SIGNATURES = {
     "bd_srv_decode_attention_ragged_tab": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _vp, _i64,
                                                  _vp]),
     "bd_srv_decode_attention_workspace_bytes": (_i64, [_ci, _ci, _ci, _ci, _ci]),
+    # the e4m3 KV cache: the scales' pointers sit behind the caches; `active` (behind pos) may be NULL
+    "bd_srv_decode_attention_kv8": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64,
+                                          _ci, _vp, _i64, _vp]),
+    "bd_srv_rope_kv_append_kv8": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _ci, _ci, _ci, _vp]),
+    "bd_srv_kv8_expand": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _vp]),
     "bd_srv_prefill_attention": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                        _vp, ctypes.c_float, _ci, _ci, _vp]),
     "bd_srv_prefill_attention_cached": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,

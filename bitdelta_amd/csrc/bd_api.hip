@@ -30,6 +30,7 @@
 #include "bd_stop_seq.h"
 #include "bd_ban.h"
 #include "bd_truncate.h"
+#include "bd_attn_kv8.h"
 #include <algorithm>
 #include <cstdlib>
 #include <atomic>
@@ -2435,4 +2436,101 @@ extern "C" int bd_srv_truncate_rows(const void* logits, int64_t sl, int V, void*
 extern "C" int bd_srv_step_truncate(const void* logits, int64_t sl, int V, void* out, int64_t so, const float* tau, const float* params,
                                     const uint8_t* active, int T, int dtype, void* stream) {
     return truncate_launch(logits, sl, V, out, so, tau, params, active, T, dtype, true, stream);
+}
+
+// (behind every kernel that existed before them: see the note above bd_srv_prefill_attention_cached)
+// The KV cache in e4m3 bytes (bd_attn_kv8.h).  ONE entry for the four forms of the 16-bit launch: s_tab = 0 is the shared table, active = NULL the
+// scalar position.  Validation in decode_attention_launch's order; the split rule, the workspace and its ticket contract are that launch's own.
+extern "C" int bd_srv_decode_attention_kv8(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                           const float* k_scale, const float* v_scale, const float* k_inv, const float* v_inv, void* valid,
+                                           const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                           int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
+    if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (T == 0) return BD_OK;
+    if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !k_scale || !v_scale || !k_inv || !v_inv || !valid || !pos || !out) return BD_E_NULL;
+    const int G = H / KVH;
+    if (head_dim != 128 || (G != 1 && G != 4 && G != 8) || s_qkv % 8 || !aligned16(QKV) || !aligned16(kcache) || !aligned16(vcache) ||
+        !aligned16(cos_t) || !aligned16(sin_t) || !aligned_to(k_scale, 4) || !aligned_to(v_scale, 4) || !aligned_to(k_inv, 4) ||
+        !aligned_to(v_inv, 4) || !aligned_to(pos, 8))
+        return BD_E_BAD_SHAPE;
+    AttnKv8Params p;
+    p.qkv = (const unsigned short*)QKV; p.cos = (const unsigned short*)cos_t; p.sin = (const unsigned short*)sin_t; p.s_tab = s_tab;
+    p.kc = (unsigned char*)kcache; p.vc = (unsigned char*)vcache; p.k_scale = k_scale; p.v_scale = v_scale; p.k_inv = k_inv; p.v_inv = v_inv;
+    p.valid = (unsigned char*)valid; p.pos = (const long long*)pos; p.active = (const unsigned char*)active;
+    p.out = (unsigned short*)out; p.T = T; p.H = H; p.KVH = KVH; p.Lc = Lc; p.s_qkv = s_qkv; p.s_out = s_out;
+    p.scale = 1.0f / sqrtf((float)head_dim);
+    const int64_t need = bd_srv_decode_attention_workspace_bytes(T, H, KVH, head_dim, Lc);
+    p.nsplit = 1;
+    if (need > 0 && ws && ws_bytes > ATTN_TICKET_BYTES && (int64_t)T * KVH * 4 <= ATTN_TICKET_BYTES) {
+        const int64_t fit = (ws_bytes - ATTN_TICKET_BYTES) / ((int64_t)T * H * (head_dim + 2) * 4);
+        int ns = attn_splits(T, KVH, Lc);
+        while (ns > 1 && ns > fit) ns >>= 1;
+        p.nsplit = ns;
+    }
+    p.tickets = (unsigned*)ws;
+    p.ws = (float*)((char*)ws + ATTN_TICKET_BYTES);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)(T * KVH), (unsigned)p.nsplit);
+    // ring depth: the 16-bit launch's bytes in flight at half-size rows -- 4 iterations up to 2048 cache rows, 8 beyond
+    const bool d4 = Lc <= 2048;
+    t_last_attention_form = p.nsplit | (d4 ? 4 : 8) << 8 | (p.nsplit <= 4 ? 4 : 16) << 16 | G << 24 | 1 << 30;
+#define BD_ATT8(DT, GG)                                                                                     \
+    do {                                                                                                    \
+        if (p.nsplit <= 4) {                                                                                \
+            if (d4) hipLaunchKernelGGL((decode_attn_kv8_kernel<DT, GG, 4, 4>), grid, dim3(512), 0, st, p);  \
+            else hipLaunchKernelGGL((decode_attn_kv8_kernel<DT, GG, 8, 4>), grid, dim3(512), 0, st, p);     \
+        } else {                                                                                            \
+            if (d4) hipLaunchKernelGGL((decode_attn_kv8_kernel<DT, GG, 4, 16>), grid, dim3(512), 0, st, p); \
+            else hipLaunchKernelGGL((decode_attn_kv8_kernel<DT, GG, 8, 16>), grid, dim3(512), 0, st, p);    \
+        }                                                                                                   \
+    } while (0)
+    if (dtype == BD_BF16) { if (G == 1) BD_ATT8(DT_BF16, 1); else if (G == 4) BD_ATT8(DT_BF16, 4); else BD_ATT8(DT_BF16, 8); }
+    else { if (G == 1) BD_ATT8(DT_F16, 1); else if (G == 4) BD_ATT8(DT_F16, 4); else BD_ATT8(DT_F16, 8); }
+#undef BD_ATT8
+    return launch_status();
+}
+
+extern "C" int bd_srv_rope_kv_append_kv8(void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                         const float* k_inv, const float* v_inv, int T, int S, int H, int KVH, int head_dim, int64_t sx, int Lc,
+                                         int pos0, int dtype, void* stream) {
+    if (T < 0 || S < 0 || H < 1 || KVH < 1 || pos0 < 0 || Lc < 1 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (T == 0 || S == 0) return BD_OK;
+    if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !k_inv || !v_inv) return BD_E_NULL;
+    if (head_dim != 128 || sx % 8 || sx < (int64_t)(H + 2 * KVH) * 128 || (int64_t)pos0 + S > Lc || (int64_t)T * S >= (1ll << 31) ||
+        !aligned16(QKV) || !aligned16(cos_t) || !aligned16(sin_t) || !aligned16(kcache) || !aligned16(vcache) || !aligned_to(k_inv, 4) ||
+        !aligned_to(v_inv, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == BD_BF16)
+        hipLaunchKernelGGL((rope_kv_append_kv8_kernel<DT_BF16>), dim3((unsigned)(T * S)), dim3(256), 0, st, (unsigned short*)QKV,
+                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (long long)s_tab, (unsigned char*)kcache,
+                           (unsigned char*)vcache, k_inv, v_inv, H, KVH, (long long)sx, S, pos0, Lc);
+    else
+        hipLaunchKernelGGL((rope_kv_append_kv8_kernel<DT_F16>), dim3((unsigned)(T * S)), dim3(256), 0, st, (unsigned short*)QKV,
+                           (const unsigned short*)cos_t, (const unsigned short*)sin_t, (long long)s_tab, (unsigned char*)kcache,
+                           (unsigned char*)vcache, k_inv, v_inv, H, KVH, (long long)sx, S, pos0, Lc);
+    return launch_status();
+}
+
+extern "C" int bd_srv_kv8_expand(const void* kcache, const void* vcache, const float* k_scale, const float* v_scale, void* k16, void* v16, int T,
+                                 int KVH, int head_dim, int Lc, int r0, int r1, int dtype, void* stream) {
+    if (T < 0 || KVH < 1 || Lc < 1 || r0 < 0 || r1 < r0 || r1 > Lc) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (T == 0 || r1 == r0) return BD_OK;
+    if (!kcache || !vcache || !k_scale || !v_scale || !k16 || !v16) return BD_E_NULL;
+    const int64_t threads = (int64_t)T * KVH * (r1 - r0) * 8;
+    if (head_dim != 128 || (int64_t)T * KVH >= (1ll << 31) || (threads + 255) / 256 >= (1ll << 31) || !aligned16(kcache) || !aligned16(vcache) ||
+        !aligned16(k16) || !aligned16(v16) || !aligned_to(k_scale, 4) || !aligned_to(v_scale, 4))
+        return BD_E_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((threads + 255) / 256), 2);
+    if (dtype == BD_BF16)
+        hipLaunchKernelGGL((kv8_expand_kernel<DT_BF16>), grid, dim3(256), 0, st, (const unsigned char*)kcache, (const unsigned char*)vcache, k_scale,
+                           v_scale, (unsigned short*)k16, (unsigned short*)v16, T * KVH, Lc, r0, r1);
+    else
+        hipLaunchKernelGGL((kv8_expand_kernel<DT_F16>), grid, dim3(256), 0, st, (const unsigned char*)kcache, (const unsigned char*)vcache, k_scale,
+                           v_scale, (unsigned short*)k16, (unsigned short*)v16, T * KVH, Lc, r0, r1);
+    return launch_status();
 }

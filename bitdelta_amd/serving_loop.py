@@ -496,13 +496,33 @@ class TenantDecoder(nn.Module):
     MIN_STOP_WIDTH = 8          # stop ids per tenant the static stop table holds before it has to grow (to the next power of two)
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
-    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None):
-        """rope: the rotary embedding (rope_spec).  None: rope_theta 10000, unscaled, one [max_len, head_dim] table pair for every tenant.  One
+    def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None,
+                 kv_cache=None, kv_scales=None):
+        """kv_cache: None keeps the KV cache in the activation dtype; "fp8" holds it in OCP e4m3 bytes (torch.float8_e4m3fn), half the resident
+        bytes and half the decode attention's stream (include/bitdelta_hip.h, bd_srv_decode_attention_kv8, states the arithmetic).  It runs on the
+        HIP arms only -- fast_glue, the HIP decode attention and hip_prefill_attention -- and refuses (ValueError here, RuntimeError at the step)
+        what they do not cover; prefetch_o is refused as a session refuses it.  An fp8 conversation is not bit-compatible with a 16-bit one.
+        kv_scales: None (every scale 1.0), or (k, v): fp32 [layers, tenants, kv_heads] each -- what kv_scales_from_cache returns -- the scales
+        new_cache() hands every cache of this decoder; load_tenant(kv_scales=) rewrites a slot's rows.
+        rope: the rotary embedding (rope_spec).  None: rope_theta 10000, unscaled, one [max_len, head_dim] table pair for every tenant.  One
         spec: one shared pair built from it (a base with another rope_theta; same launches).  A list of `tenants` specs: a pair per tenant,
         cos / sin [tenants, max_len, head_dim] -- a fine-tune's RoPE scaling is part of the fine-tune -- which load_tenant(rope=) rewrites
         row by row."""
         super().__init__()
         hd_ = cfg[0] // cfg[3]
+        if kv_cache not in (None, "fp8"):
+            raise ValueError("kv_cache = %r: None (the activation dtype) or \"fp8\"" % (kv_cache,))
+        if kv_cache is None and kv_scales is not None:
+            raise ValueError("kv_scales belong to kv_cache=\"fp8\"")
+        if kv_cache == "fp8":
+            if not ops.decode_attention_supported(cfg[3], cfg[4], hd_):
+                raise ValueError("kv_cache=\"fp8\" needs the HIP attention kernels: head_dim 128 and 1, 4 or 8 query heads per kv head")
+            if PREFETCH_O_DEFAULT:
+                raise ValueError("kv_cache=\"fp8\" does not take prefetch_o (a side branch next to the attention launch)")
+        self.kv_cache = kv_cache
+        self._kv_scales = None          # fp8: (k, v) fp32 CPU [layers, tenants, kv_heads], made at the first new_cache() (the layers come later)
+        self._kv_scales_arg = kv_scales
+        self._kv8_buf = None            # fp8: ONE 16-bit scratch pair [T, kvh, Lc, 128] per decoder, reused by every layer of a chunk (prefill_chunk)
         self.rope_per_tenant = rope is not None and not isinstance(rope, RopeSpec)
         if self.rope_per_tenant:
             specs = list(rope)
@@ -580,14 +600,15 @@ class TenantDecoder(nn.Module):
     # ---------------------------------------------------------------- construction
     @classmethod
     def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
-                  base_gptq4=False, rope=None):
+                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
         (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope: as in __init__."""
         cfg = MODEL_CONFIGS[name] if isinstance(name, str) else tuple(name)
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
-        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope)
+        self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope, kv_cache=kv_cache,
+                   kv_scales=kv_scales)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -639,12 +660,83 @@ class TenantDecoder(nn.Module):
         return sum(l.qkv.weight.numel() + l.o.weight.numel() + l.gate_up.weight.numel() + l.down.weight.numel() for l in self.layers)
 
     # ---------------------------------------------------------------- forward
-    def new_cache(self, length=None):
+    def new_cache(self, length=None, kv_cache="decoder"):
+        """kv_cache: "decoder" = this decoder's own mode; None = a 16-bit cache whatever the mode (score's scratch, a calibration prefill).  An fp8
+        cache holds float8_e4m3fn tensors (byte 0 = 0.0) and, per layer, the fp32 scales [T, kv_heads] and their host-computed reciprocals:
+        device data the kernels read at every launch, never baked into a captured graph."""
         length = length or self.max_len
         _, _, _, heads, kvh, _ = self.cfg
-        mk = lambda: torch.zeros(self.T, kvh, length, self.hd, device=self.dev, dtype=self.dtype)
-        return {"k": [mk() for _ in self.layers], "v": [mk() for _ in self.layers],
-                "valid": torch.zeros(self.T, length, dtype=torch.bool, device=self.dev)}
+        mode = self.kv_cache if kv_cache == "decoder" else kv_cache
+        if mode == "fp8":                                     # (zero bytes, viewed: byte 0 is 0.0)
+            mk = lambda: torch.zeros(self.T, kvh, length, self.hd, device=self.dev, dtype=torch.uint8).view(torch.float8_e4m3fn)
+        else:
+            mk = lambda: torch.zeros(self.T, kvh, length, self.hd, device=self.dev, dtype=self.dtype)
+        cache = {"k": [mk() for _ in self.layers], "v": [mk() for _ in self.layers],
+                 "valid": torch.zeros(self.T, length, dtype=torch.bool, device=self.dev)}
+        if mode == "fp8":
+            ks, vs = self._scales()
+            for name, sc in (("k", ks), ("v", vs)):
+                pairs = [ops.kv8_scale_pair(sc[li], self.dev) for li in range(len(self.layers))]
+                cache[name + "_scale"], cache[name + "_inv"] = [p[0] for p in pairs], [p[1] for p in pairs]
+        return cache
+
+    def _scales(self):
+        """the decoder's (k, v) scales, fp32 CPU [layers, tenants, kv_heads]; checked and copied from the constructor's argument on first use"""
+        if self._kv_scales is None:
+            shape = (len(self.layers), self.T, self.cfg[4])
+            if self._kv_scales_arg is None:
+                self._kv_scales = (torch.ones(shape), torch.ones(shape))
+            else:
+                k, v = (torch.as_tensor(a, dtype=torch.float32).detach().cpu().clone() for a in self._kv_scales_arg)
+                if tuple(k.shape) != shape or tuple(v.shape) != shape:
+                    raise ValueError("kv_scales: (k, v) of shape [layers, tenants, kv_heads] = %s each" % (shape,))
+                for a in (k, v):
+                    ops.kv8_scale_pair(a, "cpu")               # (refuses a scale that is not finite and positive)
+                self._kv_scales = (k, v)
+        return self._kv_scales
+
+    def _kv8_scratch(self, cache):
+        """the 16-bit pair kv8_expand fills for a chunk over this cache: the cache's own (a tenant's slices of the parent's, cache_view) or this
+        decoder's one pair, made on first use"""
+        sc = cache.get("scratch")
+        if sc is None:
+            shape = cache["k"][0].shape
+            if self._kv8_buf is None or self._kv8_buf[0].shape != shape:
+                self._kv8_buf = tuple(torch.zeros(shape, device=self.dev, dtype=self.dtype) for _ in range(2))
+            sc = self._kv8_buf
+        return sc
+
+    def _layer_kv8(self, layer, qkv, cache, li, pos_idx, ragged):
+        """_layer's attention on an fp8 cache: the three HIP arms (decode, scalar or ragged; prefill from position 0; a chunk behind cached keys);
+        there is no stock-op form to fall to"""
+        T, S, _ = qkv.shape
+        _, _, _, heads, kvh, _ = self.cfg
+        hd = self.hd
+        ck, cv = cache["k"][li], cache["v"][li]
+        ks, vs, ki, vi = cache["k_scale"][li], cache["v_scale"][li], cache["k_inv"][li], cache["v_inv"][li]
+        if not (self.fast_glue and self.hip_prefill_attention and not self.prefetch_o and qkv.is_contiguous() and ck.is_contiguous()
+                and cv.is_contiguous()):
+            raise RuntimeError("kv_cache=\"fp8\" runs on the HIP attention arms only: fast_glue and hip_prefill_attention on, prefetch_o off")
+        nq, nk = heads * hd, kvh * hd
+        if ragged is not None or (S == 1 and cache.get("chunk") is None):
+            if S != 1:
+                raise RuntimeError("a ragged decode step is one token per tenant")
+            pos, active = (ragged[0], ragged[1]) if ragged is not None else (pos_idx, None)
+            return ops.decode_attention_kv8(qkv, self.cos, self.sin, ck, cv, ks, vs, ki, vi, cache["valid"], pos, heads, kvh, active=active)
+        if cache.get("chunk") is not None:
+            # append (quantised) -> expand the rows the chunk may see into the 16-bit scratch -> the 16-bit cached prefill kernel on the scratch.
+            # kv_start is device data, so the expansion starts at row 0: a conversation's left pads are finite bytes the kernel masks
+            q0, kvs = cache["chunk"]
+            ops.rope_kv_append_kv8_(qkv, self.cos, self.sin, ck, cv, ki, vi, heads, kvh, q0)
+            k16, v16 = self._kv8_scratch(cache)
+            ops.kv8_expand(ck, cv, ks, vs, k16, v16, 0, q0 + S)
+            return ops.prefill_attention_cached(qkv[..., :nq].view(T, S, heads, hd), k16, v16, q0, kv_start=kvs)
+        if cache.get("kv_start") is not None and S % 64 == 0:
+            # prefill from position 0: the whole-prompt attention keeps reading the unquantised q / k / v of the projection output
+            ops.rope_kv_append_kv8_(qkv, self.cos, self.sin, ck, cv, ki, vi, heads, kvh, 0)
+            return ops.prefill_attention(qkv[..., :nq].view(T, S, heads, hd), qkv[..., nq:nq + nk].view(T, S, kvh, hd),
+                                         qkv[..., nq + nk:].view(T, S, kvh, hd), kv_start=cache["kv_start"], causal=True)
+        raise RuntimeError("kv_cache=\"fp8\": a prefill from position 0 takes left-padded prompts of a multiple of 64 rows (prepare())")
 
     # prefill: the HIP per-tenant RMSNorm (ONE launch).  Its block-per-row form is used up to this many rows and stock torch beyond (F.rms_norm +
     # the weight multiply = three launches, but faster per row on long prompts: 2048-row prefill 8.5 vs 13.1 us, profiles/r03_prefill_glue.txt);
@@ -772,7 +864,7 @@ class TenantDecoder(nn.Module):
         return self.cos[pos_idx], self.sin[pos_idx]
 
     @torch.no_grad()
-    def load_tenant(self, t, state, tag=None, rope=None):
+    def load_tenant(self, t, state, tag=None, rope=None, kv_scales=None):
         """Replace the fine-tune in slot t IN PLACE (state: see tenant_state): every delta Linear's sign words and scales through
         FusedDeltaLinear.load_tenant, the tenant's rows of the norms, the embedding and the lm_head by copies on the current stream.  Storage and
         pointers stay, so captured decode steps stay valid and the other tenants' rows are not touched.  The one thing a captured step bakes that
@@ -791,10 +883,14 @@ class TenantDecoder(nn.Module):
         the whole slot, positional encoding included.  On a decoder with per-tenant tables the rows cos[t] / sin[t] are rebuilt on the device
         and copied in place on the current stream (no host read; storage, pointers and captured graphs stay valid).  On a decoder with one
         shared table a spec other than the decoder's is refused (ValueError) before the first write.  Keys of slot t that are still in a
-        cache were rotated with the old table: they are not reusable (TenantSession.load_tenant forgets them)."""
+        cache were rotated with the old table: they are not reusable (TenantSession.load_tenant forgets them).
+        kv_scales (kv_cache="fp8" only): the slot's cache scales afterwards, (k, v) fp32 [layers, kv_heads] each; None, the default, is 1.0 --
+        a load defines the whole slot.  The slot's rows of the decoder's cache scales and reciprocals are rewritten in place on the current
+        stream: pointers stay and no kernel bakes a scale, so no captured graph is dropped for them."""
         if tag is not None:
             hash(tag)
         self._check_state(t, state)
+        new_scales = self._load_kv_scales(kv_scales)
         spec = self._load_rope(t, rope)
         require_gpu(self.embed)
         assert not torch.cuda.is_current_stream_capturing(), "a load reads the hand-off scale on the host: not inside a graph capture"
@@ -815,6 +911,14 @@ class TenantDecoder(nn.Module):
             self.cos[t].copy_(cos)
             self.sin[t].copy_(sin)
             self._rope[t] = spec
+        if new_scales is not None:
+            for own, new, name in zip(self._scales(), new_scales, ("k", "v")):
+                own[:, t] = new
+                if self._kv_cache is not None:
+                    for li in range(len(self.layers)):
+                        sc, inv = ops.kv8_scale_pair(new[li], self.dev)
+                        self._kv_cache[name + "_scale"][li][t].copy_(sc)
+                        self._kv_cache[name + "_inv"][li][t].copy_(inv)
         # The decoder's own one-tenant view is dropped and rebuilt on its next use.  That is enough: a view slices this storage and caches nothing
         # derived from tenant data (it only prefills, where no hand-off norm is made), so a view a caller still holds reads the new fine-tune too.
         self._tenant_views.pop(t, None)
@@ -826,6 +930,22 @@ class TenantDecoder(nn.Module):
             for sess in list(self._sessions):
                 sess._graphs.clear()
         return rescaled
+
+    def _load_kv_scales(self, kv_scales):
+        """load_tenant's check of its kv_scales argument, before the first write: None on a 16-bit decoder, else (k, v) fp32 CPU [layers, kv_heads]"""
+        if self.kv_cache is None:
+            if kv_scales is not None:
+                raise ValueError("kv_scales belong to kv_cache=\"fp8\"")
+            return None
+        shape = (len(self.layers), self.cfg[4])
+        if kv_scales is None:
+            return torch.ones(shape), torch.ones(shape)
+        k, v = (torch.as_tensor(a, dtype=torch.float32).detach().cpu() for a in kv_scales)
+        if tuple(k.shape) != shape or tuple(v.shape) != shape:
+            raise ValueError("kv_scales: (k, v) of shape [layers, kv_heads] = %s each" % (shape,))
+        for a in (k, v):
+            ops.kv8_scale_pair(a, "cpu")
+        return k, v
 
     def _layer(self, layer, x, cos, sin, cache, li, pos_idx, attn_mask, ssq_valid=False, next_layer=None, h_in=None, ragged=None):
         """one decoder layer; returns (x, ssq_valid): whether self._ssq / self._xw hold the partial sums of squares of the returned x and its
@@ -861,7 +981,9 @@ class TenantDecoder(nn.Module):
             with torch.cuda.stream(pf):
                 w_o = layer.o.weight_tiled if (layer.o.weight_tiled is not None and layer.o.use_tiled) else layer.o.weight
                 ops.cache_warm(w_o, layer.o.mask_packed)
-        if ragged is not None:
+        if ck.dtype == torch.float8_e4m3fn:
+            a = self._layer_kv8(layer, qkv, cache, li, pos_idx, ragged)
+        elif ragged is not None:
             # a session's step: the same launch with each tenant at its own position; there is no stock-op form of it to fall to
             if not (S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd)):
                 raise RuntimeError("a ragged decode step needs the HIP decode attention (fast_glue, head_dim 128, 1 / 4 / 8 query heads per kv head)")
@@ -1074,7 +1196,7 @@ class TenantDecoder(nn.Module):
                 rows[t, :c] = torch.arange(pad + f - 1, L - 1)
                 labels[t, :c] = ids[t, pad + f:]
         ids, am, rows, labels = ids.to(self.dev), am.to(self.dev), rows.to(self.dev), labels.to(self.dev)
-        x = self.prefill(ids, am, self.new_cache(L), hidden=True)
+        x = self.prefill(ids, am, self.new_cache(L, kv_cache=None), hidden=True)       # (its own 16-bit scratch cache, whatever the decoder's mode)
         t_idx = torch.arange(T, device=self.dev).view(T, 1)
         h = self._norm(x[t_idx, rows], self.final_norm)                      # [T, M, hidden]: the predicting rows only
         head_t = self.lm_head.transpose(1, 2)
@@ -1158,6 +1280,8 @@ class TenantDecoder(nn.Module):
         width = max(self.MIN_STOP_WIDTH, 1 << max(nstop - 1, 0).bit_length())
         key = (width, self.fast_glue, self.fuse_glue, self.fuse_qkv_norm, self.fuse_gateup_norm, self.norm_handoff, FusedDeltaLinear.use_tiled,
                self.prefetch_o, self.step_kernels)
+        if self.kv_cache is not None:                         # (a 16-bit decoder keeps the key it had)
+            key = key + (self.kv_cache,)
         if self._kv_cache is None:
             self._kv_cache = self.new_cache()
         slot = self._static.pop(key, None)
@@ -1214,7 +1338,7 @@ class TenantDecoder(nn.Module):
         v = views.get(t)
         if v is None:
             v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4,
-                              rope=self._rope[t])
+                              rope=self._rope[t], kv_cache=self.kv_cache)
             # the parent's table, or the tenant's rows of it: a slice of the storage load_tenant(rope=) rewrites in place
             v.cos, v.sin = (self.cos[t], self.sin[t]) if self.rope_per_tenant else (self.cos, self.sin)
             for layer in self.layers:
@@ -1231,7 +1355,12 @@ class TenantDecoder(nn.Module):
 
     def cache_view(self, cache, t):
         """tenant t's slices of a KV cache of this decoder (views, no copy): what tenant_view(t) prefills into"""
-        return {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
+        view = {"k": [k[t:t + 1] for k in cache["k"]], "v": [v[t:t + 1] for v in cache["v"]], "valid": cache["valid"][t:t + 1]}
+        if "k_scale" in cache:                                # an fp8 cache: the tenant's rows of the scales, and of this decoder's one scratch pair
+            for name in ("k_scale", "k_inv", "v_scale", "v_inv"):
+                view[name] = [s[t:t + 1] for s in cache[name]]
+            view["scratch"] = tuple(s[t:t + 1] for s in self._kv8_scratch(cache))
+        return view
 
     def session(self, max_stop_ids=8, sampling=False, logprobs=None, penalties=False, max_logit_bias=16, constraints=False,
                 max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8, bans=False, max_bad_words=16,
@@ -1283,6 +1412,15 @@ class TenantDecoder(nn.Module):
             st[k].copy_(v)
         st["cache"]["valid"].copy_(snap_valid)
         return g.replay
+
+
+def kv_scales_from_cache(cache16, floor=2.0 ** -20):
+    """Calibration of kv_cache="fp8": from a 16-bit cache after a calibration prefill (new_cache(kv_cache=None)), per (layer, tenant, kv head) the
+    largest |value| over the valid rows divided by 448, never below `floor` -- so that the calibration's largest element lands on e4m3's largest.
+    Returns (k, v), fp32 CPU [layers, tenants, kv_heads] each: TenantDecoder(kv_scales=), or row [:, t] for load_tenant(t, kv_scales=)."""
+    valid = cache16["valid"][:, None, :, None]
+    amax = lambda c: torch.where(valid, c.float().abs(), torch.zeros((), device=c.device)).amax(dim=(2, 3))
+    return tuple(torch.stack([(amax(c) / ops.KV8_MAX).clamp_min(floor) for c in cache16[name]]).cpu() for name in ("k", "v"))
 
 
 def extend_plan(pos, kv_start, done, n_tokens, Lc, active=False):
@@ -1776,7 +1914,7 @@ class TenantSession:
 
     # ------------------------------------------------------------ admission
     @torch.no_grad()
-    def load_tenant(self, t, state, tag=None, rope=None):
+    def load_tenant(self, t, state, tag=None, rope=None, kv_scales=None):
         """Put another fine-tune into slot t (TenantDecoder.load_tenant) while the other tenants keep generating: refused (RuntimeError) while
         tenant t is active.  Runs on the current stream, i.e. ordered between the replays around it; tenant t's validity bytes, stop reason, token
         count and output row are cleared, nobody else's state, cache rows or validity bytes are touched.  Host reads: tenant t's own activity
@@ -1784,14 +1922,15 @@ class TenantSession:
         tag: the slot's fine-tune tag afterwards (TenantDecoder.load_tenant, tenant_tag); a refused load leaves the tag as it was.
         rope: the slot's rotary embedding afterwards (rope_spec; None = the decoder's default), as TenantDecoder.load_tenant takes it: on per-tenant
         tables the slot's rows are rewritten in place, so the session's captured graphs stay; a shared-table decoder refuses another spec before
-        anything is written.  The slot's cached keys were rotated with the old table: extend() after a load refuses, as before."""
+        anything is written.  The slot's cached keys were rotated with the old table: extend() after a load refuses, as before.
+        kv_scales: the slot's fp8 cache scales afterwards (TenantDecoder.load_tenant): rewritten in place, the captured graphs stay."""
         if not (isinstance(t, int) and 0 <= t < self.T):
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
         if tag is not None:
             hash(tag)
         if bool(self.active_flags[t]):
             raise RuntimeError("tenant %d is still generating" % t)
-        rescaled = self.dec.load_tenant(t, state, tag=tag, rope=rope)
+        rescaled = self.dec.load_tenant(t, state, tag=tag, rope=rope, kv_scales=kv_scales)
         self._kv_start[t] = None                      # the cache rows belong to the fine-tune that left: nothing to extend
         self.cache["valid"][t].zero_()
         self.done[t] = 0
@@ -2287,6 +2426,8 @@ class TenantSession:
             key = key + ("bans", self.ban_tok.shape[1], self.ban_tok.shape[2])
         if self.truncation:                           # (likewise)
             key = key + ("truncation",)
+        if dec.kv_cache is not None:                  # (likewise: another attention launch; its scales are device data)
+            key = key + (dec.kv_cache,)
         g = self._graphs.get(key)
         if g is None:
             if dec._capture_stream is None:

@@ -748,3 +748,80 @@ def rope_kv_append_(qkv, cos, sin, kcache, vcache, heads, kvh, pos0=0):
         check(lib().bd_srv_rope_kv_append(ptr(qkv), ptr(cos), ptr(sin), ptr(kcache), ptr(vcache), T, S, heads, kvh, 128, qkv.stride(1), Lc, pos0,
                                           DTYPE_CODE[qkv.dtype], stream_ptr()), "srv_rope_kv_append")
     return qkv
+
+
+# ---- the KV cache in e4m3 bytes (csrc/bd_attn_kv8.h; include/bitdelta_hip.h states the definition)
+KV8_MAX = 448.0
+
+
+def kv8_scale_pair(scale, device):
+    """(scale, 1 / scale) as fp32 device tensors: the reciprocal is computed on the host, in fp32, once -- no kernel divides by a scale"""
+    s = torch.as_tensor(scale, dtype=torch.float32).detach().cpu().contiguous()
+    if not bool((torch.isfinite(s) & (s > 0)).all()):
+        raise ValueError("a KV-cache scale is a finite positive number")
+    return s.to(device), torch.reciprocal(s).to(device)
+
+
+def _kv8_args(kcache, vcache, T, kv_heads, *scales):
+    assert kcache.dtype == torch.float8_e4m3fn and vcache.dtype == torch.float8_e4m3fn, "an fp8 KV cache is torch.float8_e4m3fn"
+    assert kcache.dim() == 4 and kcache.shape[:2] == (T, kv_heads) and kcache.shape[3] == 128 and vcache.shape == kcache.shape
+    assert kcache.is_contiguous() and vcache.is_contiguous()
+    for s in scales:
+        assert s.dtype == torch.float32 and s.shape == (T, kv_heads) and s.is_contiguous(), "scales are fp32 [T, kv_heads]"
+
+
+def decode_attention_kv8(qkv, cos, sin, kcache, vcache, k_scale, v_scale, k_inv, v_inv, valid, pos, heads, kv_heads, active=None):
+    """decode_attention (active None: pos has one element) or decode_attention_ragged (active bool [T], pos [T]) on float8_e4m3fn caches
+    [T, kv_heads, Lc, 128] with fp32 scales [T, kv_heads] and their host-computed reciprocals (kv8_scale_pair).  The new key and value are
+    quantised, appended and attended to as their bytes.  cos / sin [Lmax, 128] or per tenant [T, Lmax, 128].  Returns [T, 1, heads * 128]."""
+    T = qkv.shape[0]
+    s_tab = table_stride(cos, sin, T)
+    require_gpu(qkv, cos, sin, kcache, vcache, k_scale, v_scale, k_inv, v_inv, valid, pos, active)
+    _kv8_args(kcache, vcache, T, kv_heads, k_scale, v_scale, k_inv, v_inv)
+    assert qkv.shape[1] == 1 and qkv.shape[2] == (heads + 2 * kv_heads) * 128 and qkv.stride(2) == 1
+    assert valid.is_contiguous() and valid.dtype == torch.bool and valid.shape == (T, kcache.shape[2])
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == qkv.dtype and pos.dtype == torch.int64 and pos.is_contiguous()
+    if active is None:
+        assert pos.numel() == 1
+    else:
+        assert pos.numel() == T and active.dtype == torch.bool and active.numel() == T and active.is_contiguous()
+    out = torch.empty((T, 1, heads * 128), device=qkv.device, dtype=qkv.dtype)
+    L = lib()
+    need = L.bd_srv_decode_attention_workspace_bytes(T, heads, kv_heads, 128, kcache.shape[2])
+    ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)          # (the 16-bit launch's persistent scratch, same contract)
+    with torch.cuda.device(qkv.device):
+        check(L.bd_srv_decode_attention_kv8(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(k_scale), ptr(v_scale), ptr(k_inv),
+                                            ptr(v_inv), ptr(valid), ptr(pos), ptr(active), ptr(out), T, heads, kv_heads, 128, kcache.shape[2],
+                                            qkv.stride(0), out.stride(0), DTYPE_CODE[qkv.dtype], ptr(ws), need, stream_ptr()),
+              "srv_decode_attention_kv8")
+    return out
+
+
+def rope_kv_append_kv8_(qkv, cos, sin, kcache, vcache, k_inv, v_inv, heads, kvh, pos0=0):
+    """rope_kv_append_ on float8_e4m3fn caches: q and k of qkv [T, S, (heads + 2 kvh) * 128] are rotated in place exactly as there, and the rotated
+    k rows and the v rows go to the caches as bytes, quantised with the reciprocal scales k_inv / v_inv (fp32 [T, kvh]).  Returns qkv."""
+    T, S, W = qkv.shape
+    s_tab = table_stride(cos, sin, T)
+    require_gpu(qkv, cos, sin, kcache, vcache, k_inv, v_inv)
+    _kv8_args(kcache, vcache, T, kvh, k_inv, v_inv)
+    assert W == (heads + 2 * kvh) * 128 and qkv.stride(2) == 1 and (T == 1 or qkv.stride(0) == S * qkv.stride(1))
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == qkv.dtype and cos.shape[-2] >= pos0 + S
+    Lc = kcache.shape[2]
+    assert pos0 + S <= Lc
+    with torch.cuda.device(qkv.device):
+        check(lib().bd_srv_rope_kv_append_kv8(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(k_inv), ptr(v_inv), T, S, heads, kvh,
+                                              128, qkv.stride(1), Lc, pos0, DTYPE_CODE[qkv.dtype], stream_ptr()), "srv_rope_kv_append_kv8")
+    return qkv
+
+
+def kv8_expand(kcache, vcache, k_scale, v_scale, k16, v16, r0, r1):
+    """Rows r0 .. r1 - 1 of the float8_e4m3fn caches [T, kvh, Lc, 128], times their scales (fp32 [T, kvh]), rounded into the 16-bit tensors
+    k16 / v16 of the same shape (contiguous); every other row of k16 / v16 keeps its bits."""
+    T, kvh = kcache.shape[:2]
+    require_gpu(kcache, vcache, k_scale, v_scale, k16, v16)
+    _kv8_args(kcache, vcache, T, kvh, k_scale, v_scale)
+    assert k16.shape == kcache.shape and v16.shape == kcache.shape and k16.dtype == v16.dtype and k16.dtype in (torch.float16, torch.bfloat16)
+    assert k16.is_contiguous() and v16.is_contiguous() and 0 <= r0 <= r1 <= kcache.shape[2]
+    with torch.cuda.device(kcache.device):
+        check(lib().bd_srv_kv8_expand(ptr(kcache), ptr(vcache), ptr(k_scale), ptr(v_scale), ptr(k16), ptr(v16), T, kvh, 128, kcache.shape[2],
+                                      int(r0), int(r1), DTYPE_CODE[k16.dtype], stream_ptr()), "srv_kv8_expand")

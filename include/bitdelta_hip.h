@@ -679,6 +679,48 @@ int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* V
  * back to zero, so a buffer that is zero-filled once and used by one stream at a time can be reused by every call. */
 int64_t bd_srv_decode_attention_workspace_bytes(int T, int H, int KVH, int head_dim, int Lc);
 
+/* ---- The KV cache in 8 bits (serving_loop.TenantDecoder(kv_cache="fp8"); kernels in csrc/bd_attn_kv8.h).  DEFINITION, which the tests hold the
+ * kernels to:
+ * Format.  OCP e4m3fn: 1 sign, 4 exponent bits (bias 7), 3 mantissa bits; largest finite value 448; no infinity; 0x7f / 0xff = NaN.  The caches
+ *   are bytes [T, KVH, Lc, 128] (torch.float8_e4m3fn on the host); valid [T, Lc] as for the 16-bit cache.
+ * Scales.  k_scale, v_scale: fp32 [T, KVH], one pair per layer -- a fine-tune shifts activations, so a scale belongs to the tenant slot.  Next to
+ *   each the caller passes its reciprocal k_inv, v_inv, fp32 [T, KVH], computed on the host (the r / 1/r rule of bd_srv_penalize_rows): no
+ *   kernel divides by a scale.  1.0 is the neutral value.
+ * Quantise a 16-bit value x (the rotated key exactly as the 16-bit entries would store it; the value as it lies in QKV):
+ *     byte = e4m3_rne(clamp(float(x) * inv_scale, -448, +448))
+ *   one fp32 product, an explicit fp32 clamp in front of the conversion (nothing relies on the conversion's saturation mode), round to nearest
+ *   even, subnormals kept.  NaN stays NaN (the clamp passes it).
+ * Dequantise: float(byte) * scale, in fp32 (the conversion is exact).
+ * bd_srv_decode_attention_kv8: bd_srv_decode_attention_tab (active == NULL: pos is ONE device scalar) or bd_srv_decode_attention_ragged_tab
+ *   (active [T] bytes, pos [T]) on byte caches; s_tab = 0 is the one shared table pair.  It rotates q and the new key exactly as those entries do,
+ *   quantises the new key and value, writes their bytes at the position and marks valid, and attends over the cache AS IT STANDS AFTER THE
+ *   APPEND: the new token takes part as its dequantised bytes.  out is therefore a function of q, the cache bytes, the scales and valid, and
+ *   the token weighs in this step what it will weigh in the next.  softmax in fp32 over q . (float(kbyte) * k_scale) / sqrt(128); out =
+ *   round16(sum_k p_k float(vbyte_k) * v_scale).  Split rule, workspace, ticket contract (bd_srv_decode_attention_workspace_bytes) and the
+ *   deterministic in-launch merge are the 16-bit entries'.  A tenant with active[t] == 0, or a position outside [0, Lc) IN EITHER FORM, stays out:
+ *   zeros to its H*128 outputs, no byte, no mark, no partial, no ticket.
+ *   Checked before any device call, in this order: T < 0, H < 1, KVH < 1, H % KVH, Lc < 1, s_tab < 0 or s_tab % 8 -> BD_E_BAD_SHAPE; dtype not
+ *   fp16 / bf16 -> BD_E_BAD_DTYPE; T == 0 -> BD_OK; a pointer other than active / ws NULL (the four scale pointers included) -> BD_E_NULL;
+ *   head_dim != 128, H / KVH not in {1, 4, 8}, s_qkv % 8, QKV / a cache / a table not 16-byte aligned, a scale pointer not 4-byte or pos not
+ *   8-byte aligned -> BD_E_BAD_SHAPE.  bd_last_attention_form() afterwards: nsplit | DEPTH << 8 | MAXS << 16 | G << 24 | 1 << 30.
+ * bd_srv_rope_kv_append_kv8: bd_srv_rope_kv_append_tab on byte caches -- q and k of QKV are rotated in place, bit for bit as there (the
+ *   whole-prompt attention keeps reading 16-bit q / k / v from QKV), and the rotated k rows and the v rows are quantised into the caches at
+ *   positions pos0 .. pos0 + S - 1.  Checks as there; k_inv / v_inv NULL -> BD_E_NULL.
+ * bd_srv_kv8_expand: k16 / v16 [T, KVH, Lc, 128] 16-bit (contiguous, like the caches): rows r0 .. r1 - 1 of every (tenant, head) become
+ *   round16(float(byte) * scale); every other row keeps its bits.  What bd_srv_prefill_attention_cached then reads when a chunk continues an
+ *   8-bit conversation: the history passes through one more 16-bit rounding there than in the decode launch.  r0 < 0, r1 < r0, r1 > Lc ->
+ *   BD_E_BAD_SHAPE; dtype; T == 0 or r0 == r1 -> BD_OK; NULL -> BD_E_NULL; head_dim != 128 or a pointer not aligned (16 bytes, scales 4) ->
+ *   BD_E_BAD_SHAPE. */
+int bd_srv_decode_attention_kv8(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                const float* k_scale, const float* v_scale, const float* k_inv, const float* v_inv, void* valid,
+                                const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc, int64_t s_qkv,
+                                int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream);
+int bd_srv_rope_kv_append_kv8(void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, const float* k_inv,
+                              const float* v_inv, int T, int S, int H, int KVH, int head_dim, int64_t sx, int Lc, int pos0, int dtype,
+                              void* stream);
+int bd_srv_kv8_expand(const void* kcache, const void* vcache, const float* k_scale, const float* v_scale, void* k16, void* v16, int T, int KVH,
+                      int head_dim, int Lc, int r0, int r1, int dtype, void* stream);
+
 /* bytes of scratch bd_delta_bmm / bd_binary_linear may need for this problem (split-k partials of the decode path) */
 int64_t bd_gemm_workspace_bytes(int B, int M, int N, int K);
 
