@@ -92,6 +92,13 @@ SIGNATURES = {
                                        _vp, ctypes.c_float, _ci, _ci, _vp]),
     "bd_srv_prefill_attention_cached": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                               _i64, _i64, _vp, ctypes.c_float, _ci, _vp]),
+    # sliding-window attention: `window` sits behind dtype (decode) / behind scale (prefill); `active` may be NULL, s_tab 0
+    "bd_srv_decode_attention_window": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _ci, _ci, _vp,
+                                             _i64, _vp]),
+    "bd_srv_prefill_attention_window": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                              _vp, ctypes.c_float, _ci, _ci, _vp]),
+    "bd_srv_prefill_attention_cached_window": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                     _i64, _i64, _i64, _vp, ctypes.c_float, _ci, _ci, _vp]),
     "bd_gemm_workspace_bytes": (_i64, [_ci, _ci, _ci, _ci]),
     "bd_binarize": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _i64, _vp]),
     "bd_binarize_workspace_bytes": (_i64, [_i64, _i64]),

@@ -1987,11 +1987,13 @@ extern "C" int64_t bd_srv_decode_attention_workspace_bytes(int T, int H, int KVH
 // launch at equal positions has the scalar launch's geometry).  RAGGED: pos is [T] and `active` [T] bytes.
 // s_tab: tenant stride of the rotary tables (the *_tab entries; the shared-table entries pass 0 and tab_entry = false, which keeps their
 // validation as it was: they never asked for aligned tables, the kernel reads them element by element).
-template <bool RAGGED>
+// WINDOW (bd_srv_decode_attention_window): the same body once more; `window` joins the first shape checks, the split and depth rules take the rows
+// a launch can hold, Lh = min(Lc, window), and the kernels are the WINDOW = true instantiations on the MAXS = 16 merge body (bd_serving.h).
+template <bool RAGGED, bool WINDOW = false>
 static int decode_attention_launch(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, bool tab_entry, void* kcache, void* vcache,
                                    void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
-                                   int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream) {
-    if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1 || !tab_stride_ok(s_tab)) return BD_E_BAD_SHAPE;
+                                   int64_t s_qkv, int64_t s_out, int dtype, void* ws, int64_t ws_bytes, void* stream, int window = 0) {
+    if (T < 0 || H < 1 || KVH < 1 || H % KVH || Lc < 1 || !tab_stride_ok(s_tab) || (WINDOW && window < 1)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (T == 0) return BD_OK;
     if (!QKV || !cos_t || !sin_t || !kcache || !vcache || !valid || !pos || !out || (RAGGED && !active)) return BD_E_NULL;
@@ -1999,7 +2001,9 @@ static int decode_attention_launch(const void* QKV, const void* cos_t, const voi
     if (head_dim != 128 || (G != 1 && G != 4 && G != 8) || s_qkv % 8 || !aligned16(QKV) || !aligned16(kcache) || !aligned16(vcache) ||
         (tab_entry && (!aligned16(cos_t) || !aligned16(sin_t))))
         return BD_E_BAD_SHAPE;                         // other head geometries: the caller keeps its torch attention
-    AttnParams p;
+    typename AttnParamsOf<WINDOW>::type p;
+    if constexpr (WINDOW) p.window = window;
+    const int Lh = WINDOW && window < Lc ? window : Lc;          // key rows one launch can hold
     p.qkv = (const unsigned short*)QKV; p.cos = (const unsigned short*)cos_t; p.sin = (const unsigned short*)sin_t; p.s_tab = s_tab;
     p.kc = (unsigned short*)kcache; p.vc = (unsigned short*)vcache; p.valid = (unsigned char*)valid; p.pos = (const long long*)pos;
     p.active = (const unsigned char*)active;
@@ -2014,7 +2018,7 @@ static int decode_attention_launch(const void* QKV, const void* cos_t, const voi
     p.nsplit = 1;
     if (need > 0 && ws && ws_bytes > ATTN_TICKET_BYTES && (int64_t)T * KVH * 4 <= ATTN_TICKET_BYTES) {
         const int64_t fit = (ws_bytes - ATTN_TICKET_BYTES) / ((int64_t)T * H * (head_dim + 2) * 4);
-        int ns = attn_splits(T, KVH, Lc);
+        int ns = attn_splits(T, KVH, Lh);
         while (ns > 1 && ns > fit) ns >>= 1;
         p.nsplit = ns;
     }
@@ -2024,12 +2028,17 @@ static int decode_attention_launch(const void* QKV, const void* cos_t, const voi
     dim3 grid((unsigned)(T * KVH), (unsigned)p.nsplit);
 #define BD_ATT(DT, GG)                                                                                      \
     do {                                                                                                    \
-        const bool d2_ = g_attn_depth ? g_attn_depth == 2 : Lc <= 2048;                                                    \
-        t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | (p.nsplit <= 4 ? 4 : 16) << 16 | GG << 24;                 \
-        if (p.nsplit <= 4) {                                                                                               \
+        const bool d2_ = g_attn_depth ? g_attn_depth == 2 : Lh <= 2048;                                                    \
+        if constexpr (WINDOW) {                                                                                            \
+            t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | 16 << 16 | GG << 24;                                   \
+            if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 16, RAGGED, true>), grid, dim3(512), 0, st, p);             \
+            else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 16, RAGGED, true>), grid, dim3(512), 0, st, p);                 \
+        } else if (p.nsplit <= 4) {                                                                                        \
+            t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | 4 << 16 | GG << 24;                                    \
             if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 4, RAGGED>), grid, dim3(512), 0, st, p);                    \
             else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 4, RAGGED>), grid, dim3(512), 0, st, p);                        \
         } else {                                                                                                           \
+            t_last_attention_form = p.nsplit | (d2_ ? 2 : 4) << 8 | 16 << 16 | GG << 24;                                   \
             if (d2_) hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 2, 16, RAGGED>), grid, dim3(512), 0, st, p);                   \
             else hipLaunchKernelGGL((decode_attn_kernel<DT, GG, 4, 16, RAGGED>), grid, dim3(512), 0, st, p);                       \
         }                                                                                                                  \
@@ -2072,11 +2081,13 @@ extern "C" int bd_srv_decode_attention_ragged_tab(const void* QKV, const void* c
                                          s_out, dtype, ws, ws_bytes, stream);
 }
 
-extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
-                                        int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs,
-                                        int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int causal, int dtype,
-                                        void* stream) {
-    if (B < 0 || S < 0 || H < 1 || KVH < 1 || H % KVH) return BD_E_BAD_SHAPE;
+// bd_srv_prefill_attention and its windowed form (always causal): ONE body, as for the decode entries
+template <bool WINDOW>
+static int prefill_attention_launch(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
+                                    int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs,
+                                    int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int causal, int window, int dtype,
+                                    void* stream) {
+    if (B < 0 || S < 0 || H < 1 || KVH < 1 || H % KVH || (WINDOW && window < 1)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (B == 0 || S == 0) return BD_OK;
     if (!Q || !K || !V || !O) return BD_E_NULL;
@@ -2084,7 +2095,8 @@ extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void
     if (head_dim != 128 || S % 64 || (sqs | sks | svs | sos | sqb | skb | svb | sob) % 8 || !aligned16(Q) || !aligned16(K) || !aligned16(V) ||
         !aligned16(O) || (int64_t)B * H * ((S + 127) / 128) > 0x7fffffffLL)
         return BD_E_BAD_SHAPE;
-    PrefillAttnParams p;
+    typename PrefillAttnParamsOf<false, WINDOW>::type p;
+    if constexpr (WINDOW) p.window = window;
     p.q = (const unsigned short*)Q; p.k = (const unsigned short*)K; p.v = (const unsigned short*)V; p.o = (unsigned short*)O;
     p.sqb = sqb; p.sqs = sqs; p.skb = skb; p.sks = sks; p.svb = svb; p.svs = svs; p.sob = sob; p.sos = sos;
     p.kv_start = kv_start; p.B = B; p.S = S; p.H = H; p.KVH = KVH; p.nqb = (S + 127) / 128;
@@ -2093,11 +2105,19 @@ extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void
     const dim3 grid((unsigned)(p.nqb * H * B));
     static std::atomic<uint64_t> lds_done[2];               // the kernel needs more than the default dynamic LDS limit
     const int di = dtype == BD_BF16 ? 1 : 0;
-    const void* fn = di ? (const void*)prefill_attn_kernel<DT_BF16> : (const void*)prefill_attn_kernel<DT_F16>;
+    const void* fn = di ? (const void*)prefill_attn_kernel<DT_BF16, false, WINDOW> : (const void*)prefill_attn_kernel<DT_F16, false, WINDOW>;
     if (!ensure_dyn_lds(fn, PREFILL_ATTN_LDS, lds_done[di])) return BD_E_LAUNCH;
-    if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
-    else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16, false, WINDOW>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16, false, WINDOW>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
     return launch_status();
+}
+
+extern "C" int bd_srv_prefill_attention(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
+                                        int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs,
+                                        int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int causal, int dtype,
+                                        void* stream) {
+    return prefill_attention_launch<false>(Q, K, V, O, B, S, H, KVH, head_dim, sqb, sqs, skb, sks, svb, svs, sob, sos, kv_start, scale, causal, 0,
+                                           dtype, stream);
 }
 
 // ------------------------------------------------------------------ binarize / merge
@@ -2151,19 +2171,21 @@ extern "C" int bd_merge_delta(void* W, int64_t ldw, const int32_t* P, const floa
 
 // (last in the file: the kernels of a code object lie in the order the host code asks for them, and the decode step is sensitive to where
 // its kernels lie -- profiles/decode_dispatch_refactor.txt; a new entry goes behind every kernel that exists)
-extern "C" int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim,
-                                               int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb,
-                                               int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int dtype,
-                                               void* stream) {
+template <bool WINDOW>
+static int prefill_attention_cached_launch(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim,
+                                           int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb,
+                                           int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int window,
+                                           int dtype, void* stream) {
     // every check below is host arithmetic: nothing touches the device before the geometry is known to be the kernel's
-    if (B < 0 || H < 1 || KVH < 1 || H % KVH || Sq < 1 || q0 < 0 || Lc < 1 || (int64_t)q0 + Sq > Lc) return BD_E_BAD_SHAPE;
+    if (B < 0 || H < 1 || KVH < 1 || H % KVH || Sq < 1 || q0 < 0 || Lc < 1 || (int64_t)q0 + Sq > Lc || (WINDOW && window < 1)) return BD_E_BAD_SHAPE;
     if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
     if (B == 0) return BD_OK;
     if (!Q || !Kc || !Vc || !O) return BD_E_NULL;
     if (head_dim != 128 || (sqb | sqs | skb | skh | sks | svb | svh | svs | sob | sos) % 8 || !aligned16(Q) || !aligned16(Kc) || !aligned16(Vc) ||
         !aligned16(O) || (int64_t)B * H * ((Sq + 127) / 128) > 0x7fffffffLL)
         return BD_E_BAD_SHAPE;
-    PrefillAttnCachedParams p;
+    typename PrefillAttnParamsOf<true, WINDOW>::type p;
+    if constexpr (WINDOW) p.window = window;
     p.q = (const unsigned short*)Q; p.k = (const unsigned short*)Kc; p.v = (const unsigned short*)Vc; p.o = (unsigned short*)O;
     p.sqb = sqb; p.sqs = sqs; p.skb = skb; p.skh = skh; p.sks = sks; p.svb = svb; p.svh = svh; p.svs = svs; p.sob = sob; p.sos = sos;
     p.kv_start = kv_start; p.B = B; p.Sq = Sq; p.H = H; p.KVH = KVH; p.nqb = (Sq + 127) / 128; p.q0 = q0; p.Lc = Lc;
@@ -2172,11 +2194,19 @@ extern "C" int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, co
     const dim3 grid((unsigned)(p.nqb * H * B));
     static std::atomic<uint64_t> lds_done[2];               // the kernel needs more than the default dynamic LDS limit
     const int di = dtype == BD_BF16 ? 1 : 0;
-    const void* fn = di ? (const void*)prefill_attn_kernel<DT_BF16, true> : (const void*)prefill_attn_kernel<DT_F16, true>;
+    const void* fn = di ? (const void*)prefill_attn_kernel<DT_BF16, true, WINDOW> : (const void*)prefill_attn_kernel<DT_F16, true, WINDOW>;
     if (!ensure_dyn_lds(fn, PREFILL_ATTN_LDS, lds_done[di])) return BD_E_LAUNCH;
-    if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
-    else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16, true>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    if (di) hipLaunchKernelGGL((prefill_attn_kernel<DT_BF16, true, WINDOW>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
+    else hipLaunchKernelGGL((prefill_attn_kernel<DT_F16, true, WINDOW>), grid, dim3(256), PREFILL_ATTN_LDS, st, p);
     return launch_status();
+}
+
+extern "C" int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim,
+                                               int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb,
+                                               int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int dtype,
+                                               void* stream) {
+    return prefill_attention_cached_launch<false>(Q, Kc, Vc, O, B, Sq, H, KVH, head_dim, q0, Lc, sqb, sqs, skb, skh, sks, svb, svh, svs, sob, sos,
+                                                  kv_start, scale, 0, dtype, stream);
 }
 
 // (behind every kernel that existed before it: see the note above bd_srv_prefill_attention_cached)
@@ -2533,4 +2563,33 @@ extern "C" int bd_srv_kv8_expand(const void* kcache, const void* vcache, const f
         hipLaunchKernelGGL((kv8_expand_kernel<DT_F16>), grid, dim3(256), 0, st, (const unsigned char*)kcache, (const unsigned char*)vcache, k_scale,
                            v_scale, (unsigned short*)k16, (unsigned short*)v16, T * KVH, Lc, r0, r1);
     return launch_status();
+}
+
+// ---- sliding-window attention (include/bitdelta_hip.h states the semantics).  Behind every kernel that existed before them: see the note above
+// bd_srv_prefill_attention_cached.  Each entry is the windowed instantiation of its un-windowed entry's body.
+extern "C" int bd_srv_decode_attention_window(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache,
+                                              void* valid, const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim,
+                                              int Lc, int64_t s_qkv, int64_t s_out, int dtype, int window, void* ws, int64_t ws_bytes,
+                                              void* stream) {
+    // active == NULL is the lockstep form (one scalar position); s_tab == 0 the shared table pair, which is not asked to be aligned
+    if (active)
+        return decode_attention_launch<true, true>(QKV, cos_t, sin_t, s_tab, s_tab != 0, kcache, vcache, valid, pos, active, out, T, H, KVH, head_dim,
+                                                   Lc, s_qkv, s_out, dtype, ws, ws_bytes, stream, window);
+    return decode_attention_launch<false, true>(QKV, cos_t, sin_t, s_tab, s_tab != 0, kcache, vcache, valid, pos, nullptr, out, T, H, KVH, head_dim,
+                                                Lc, s_qkv, s_out, dtype, ws, ws_bytes, stream, window);
+}
+
+extern "C" int bd_srv_prefill_attention_window(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
+                                               int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs, int64_t sob,
+                                               int64_t sos, const int32_t* kv_start, float scale, int window, int dtype, void* stream) {
+    return prefill_attention_launch<true>(Q, K, V, O, B, S, H, KVH, head_dim, sqb, sqs, skb, sks, svb, svs, sob, sos, kv_start, scale, 1, window,
+                                          dtype, stream);
+}
+
+extern "C" int bd_srv_prefill_attention_cached_window(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH,
+                                                      int head_dim, int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks,
+                                                      int64_t svb, int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start,
+                                                      float scale, int window, int dtype, void* stream) {
+    return prefill_attention_cached_launch<true>(Q, Kc, Vc, O, B, Sq, H, KVH, head_dim, q0, Lc, sqb, sqs, skb, skh, sks, svb, svh, svs, sob, sos,
+                                                 kv_start, scale, window, dtype, stream);
 }

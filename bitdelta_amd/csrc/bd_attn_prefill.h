@@ -57,14 +57,33 @@ struct PrefillAttnCachedParams {
     float c;                       // softmax scale * log2(e)
 };
 
-template <bool CACHED>
+// WINDOW (sliding-window attention, both forms; always causal): the query at position i sees key j iff j <= i, i - j < W and j >= kv_start --
+// W keys INCLUDING its own, Mistral's reference implementation and the mask of current `transformers` (kv_idx > q_idx - sliding_window; older
+// releases let W + 1 keys through, which is not reproduced).  The window is a second, lower edge of the same tile walk:
+//   * workgroup: j_lo = max(ks, q_first - W + 1) / 64 with q_first the position of its first query, so a 128-query block visits at most
+//     (W + 128) / 64 + 1 tiles wherever it stands in the conversation;
+//   * wave: a tile whose last key lies below the window of the wave's FIRST query lies below every later query's window too and is skipped
+//     (wave-uniform), next to the skip past the diagonal;
+//   * lane: the mask pass also runs on tiles that reach below the window of the wave's LAST query and masks key_abs <= q_abs - W.
+// A row whose first visited tiles are wholly masked for it keeps m = -inf, l = 0, O = 0 through them (m_safe = 0, every p = exp2(-inf) = 0,
+// alpha multiplies zeros), so which tiles a workgroup happens to visit below a row's window does not change that row: the CACHED windowed
+// form is bit for bit the whole-prompt windowed form row for row, and W >= the key range is bit for bit the un-windowed kernel.
+// The heavy-first block order is kept: up to W it is the right one, and past W every block weighs the same, where any order is as good.
+struct PrefillAttnWindowParams : PrefillAttnParams { int window; };               // W >= 1 (the host refuses anything else)
+struct PrefillAttnCachedWindowParams : PrefillAttnCachedParams { int window; };
+
+template <bool CACHED, bool WINDOW = false>
 struct PrefillAttnParamsOf { typedef PrefillAttnParams type; };
 template <>
-struct PrefillAttnParamsOf<true> { typedef PrefillAttnCachedParams type; };
+struct PrefillAttnParamsOf<true, false> { typedef PrefillAttnCachedParams type; };
+template <>
+struct PrefillAttnParamsOf<false, true> { typedef PrefillAttnWindowParams type; };
+template <>
+struct PrefillAttnParamsOf<true, true> { typedef PrefillAttnCachedWindowParams type; };
 
-// CACHED = false is the whole-prompt kernel, instruction for instruction what it was before the parameter existed
-template <int DT, bool CACHED = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(const typename PrefillAttnParamsOf<CACHED>::type p) {
+// CACHED = false is the whole-prompt kernel, instruction for instruction what it was before the parameter existed; so is WINDOW = false
+template <int DT, bool CACHED = false, bool WINDOW = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(const typename PrefillAttnParamsOf<CACHED, WINDOW>::type p) {
     constexpr int HD = 128, QW = 32, QB = 128, KVB = 64;
     constexpr int KROW = 272, VROW = 320;
     constexpr int K_BYTES = KVB * KROW, V_BYTES = KVB * VROW, BUF = K_BYTES + V_BYTES;
@@ -118,6 +137,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         const int last_q = min(Q0 + QB, p.S) - 1;
         j_lo = ks / KVB, j_hi = (p.causal ? last_q : p.S - 1) / KVB;
     }
+    if constexpr (WINDOW) j_lo = max(ks, q0 + Q0 - p.window + 1) / KVB;      // the first key the workgroup's first query sees (ks >= 0)
 
     // register staging: thread -> 16-byte chunk (tid & 15) of keys (tid >> 4) + 16 i
     u32x4_t kst[4], vst[4];
@@ -177,6 +197,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     auto compute = [&](int buf, int j) {
         const int kv0 = j * KVB;
         if (causal && kv0 > qa0 + QW - 1) return;                       // past this wave's diagonal (wave-uniform)
+        if constexpr (WINDOW) {
+            if (kv0 + KVB - 1 <= qa0 - p.window) return;                // wholly below the window of this wave's first query, so of all
+        }
         const char* kb = lds + (uint32_t)(buf * BUF) + k_lane;             // + immediates: no per-read address arithmetic
         const char* vb = lds + (uint32_t)(buf * BUF + K_BYTES) + v_lane;
         f32x16_t sacc[2];
@@ -193,7 +216,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                 sacc[t] = mfma32<DT>(kf, qf[s], sacc[t]);
             }
         // masks: keys past the query (causal) or before the first valid key (left padding); only on tiles that straddle either edge
-        const bool edge = (causal && kv0 + KVB - 1 > qa0) || ks > kv0;
+        bool edge = (causal && kv0 + KVB - 1 > qa0) || ks > kv0;
+        if constexpr (WINDOW) edge = edge || qa0 + QW - 1 - kv0 >= p.window;  // the tile's first key is below the window of the wave's last query
         if (edge) {
             const int q_abs = [&] { if constexpr (CACHED) return q0 + min(qw0 + l31, nrows - 1); else return qw0 + l31; }();
 #pragma unroll
@@ -202,6 +226,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                 for (int r = 0; r < 16; ++r) {
                     const int key_abs = kv0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hi;
                     if ((causal && key_abs > q_abs) || key_abs < ks) sacc[t][r] = NEG_INF;
+                    if constexpr (WINDOW) {
+                        if (q_abs - key_abs >= p.window) sacc[t][r] = NEG_INF;
+                    }
                 }
         }
         float mx = sacc[0][0];

@@ -853,8 +853,27 @@ __device__ __forceinline__ float attn_ws_load(const float* src) {
 // enqueue / zero-at-exit contract holds).  pos[t] is a scalar load like *pos; the position is CLAMPED for addressing and the activity byte is
 // only looked at after the ring is in flight, so neither a dependent load nor a branch sits in front of the ring (a block that stays out has
 // fetched row 0 of its own cache for nothing).  RAGGED = false is the kernel as it was.
-template <int DT, int G, int DEPTH = 4, int MAXS = 4, bool RAGGED = false>
-__global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
+//
+// WINDOW (sliding-window attention, Mistral-7B-v0.1's sliding_window): the query at cache position i sees key j iff j <= i, i - j < W and
+// valid[j] != 0 -- W keys INCLUDING the query's own, which is Mistral's reference implementation and the mask of current `transformers`
+// (kv_idx > q_idx - sliding_window; older releases let W + 1 keys through, which is not reproduced).  Positions are cache positions: the valid
+// keys are contiguous behind the left pads, so index distance is token distance.  The block's key range is [lo, pos] with
+// lo = max(0, pos + 1 - W) and the nsplit blocks of a (tenant, kv head) pair share THAT range: nrows_all = pos + 1 - lo, split y owns
+// [lo + y * per_split, ..) -- no block streams a row no query may see, and the launch is bounded by W, not by the conversation.  lo is scalar
+// arithmetic behind the scalar load of pos, so the ring still starts without a dependent vector load or a branch in front of it.  A split
+// past the range (short windows) is empty and hands the merge m = -1e30, s = 0, as at small pos.  The window travels in AttnWindowParams,
+// which only the WINDOW = true instantiations take: WINDOW = false is the kernel as it was, argument block included.  The windowed launches
+// use the MAXS = 16 body for every split count (24 instantiations instead of 48 more); bd_last_attention_form() reports MAXS = 16 for them.
+struct AttnWindowParams : AttnParams {
+    int window;                    // W >= 1 (the host refuses anything else)
+};
+template <bool WINDOW>
+struct AttnParamsOf { typedef AttnParams type; };
+template <>
+struct AttnParamsOf<true> { typedef AttnWindowParams type; };
+
+template <int DT, int G, int DEPTH = 4, int MAXS = 4, bool RAGGED = false, bool WINDOW = false>
+__global__ void __launch_bounds__(512) decode_attn_kernel(const typename AttnParamsOf<WINDOW>::type p) {
     constexpr int ATTN_MAX_SPLITS = MAXS;
     constexpr int HD = 128, NWV = 8, RPI = 4 * NWV;
     __shared__ float q_lds[G][HD];              // rotated, pre-scaled queries
@@ -888,9 +907,18 @@ __global__ void __launch_bounds__(512) decode_attn_kernel(const AttnParams p) {
     const int kq = lane >> 4, d8 = lane & 15;
     const int slot = 4 * wave + kq;                      // this lane group's row slot (0 .. RPI-1)
     // this block's key rows [l_lo, l_hi) of 0 .. pos (whole iterations of RPI rows per split)
-    const long long nrows_all = pos + 1;
-    const long long per_split = ((nrows_all + p.nsplit - 1) / p.nsplit + RPI - 1) / RPI * RPI;
-    const long long l_lo = (long long)blockIdx.y * per_split, l_hi = l_lo + per_split < nrows_all ? l_lo + per_split : nrows_all;
+    long long nrows_all, per_split, l_lo, l_hi;
+    if constexpr (WINDOW) {                              // the splits share the window [lo, pos], not the cache
+        const long long lo = pos + 1 > (long long)p.window ? pos + 1 - p.window : 0;
+        nrows_all = pos + 1 - lo;
+        per_split = ((nrows_all + p.nsplit - 1) / p.nsplit + RPI - 1) / RPI * RPI;
+        l_lo = lo + (long long)blockIdx.y * per_split;
+        l_hi = l_lo + per_split < pos + 1 ? l_lo + per_split : pos + 1;
+    } else {
+        nrows_all = pos + 1;
+        per_split = ((nrows_all + p.nsplit - 1) / p.nsplit + RPI - 1) / RPI * RPI;
+        l_lo = (long long)blockIdx.y * per_split, l_hi = l_lo + per_split < nrows_all ? l_lo + per_split : nrows_all;
+    }
     const bool owns_new = l_lo <= pos && pos < l_hi;      // the split that holds the new token appends it to the cache
 
     // (the validity byte is kept RAW and tested where the row is used: compared here -- `ok = in && vld[lc] != 0` -- the byte load sat behind a

@@ -497,8 +497,12 @@ class TenantDecoder(nn.Module):
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
     def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None,
-                 kv_cache=None, kv_scales=None):
-        """kv_cache: None keeps the KV cache in the activation dtype; "fp8" holds it in OCP e4m3 bytes (torch.float8_e4m3fn), half the resident
+                 kv_cache=None, kv_scales=None, sliding_window=None):
+        """sliding_window: None, or W >= 1 (Mistral-7B-v0.1 and its fine-tunes: 4096): the query at cache position i attends to the keys
+        i - W + 1 .. i only -- W keys including its own, the mask of Mistral's reference implementation and of current `transformers` -- in
+        every attention branch (decode, ragged decode, whole-prompt prefill, prefill_chunk; the stock-op arms AND the same band into their
+        masks), and the decode attention launch streams W rows however long the conversation is.  The KV cache stays linear, max_len rows.
+        kv_cache: None keeps the KV cache in the activation dtype; "fp8" holds it in OCP e4m3 bytes (torch.float8_e4m3fn), half the resident
         bytes and half the decode attention's stream (include/bitdelta_hip.h, bd_srv_decode_attention_kv8, states the arithmetic).  It runs on the
         HIP arms only -- fast_glue, the HIP decode attention and hip_prefill_attention -- and refuses (ValueError here, RuntimeError at the step)
         what they do not cover; prefetch_o is refused as a session refuses it.  An fp8 conversation is not bit-compatible with a 16-bit one.
@@ -514,6 +518,14 @@ class TenantDecoder(nn.Module):
             raise ValueError("kv_cache = %r: None (the activation dtype) or \"fp8\"" % (kv_cache,))
         if kv_cache is None and kv_scales is not None:
             raise ValueError("kv_scales belong to kv_cache=\"fp8\"")
+        if sliding_window is not None:
+            sliding_window = operator.index(sliding_window)
+            if sliding_window < 1:
+                raise ValueError("sliding_window = %d: a window holds at least the query's own key" % sliding_window)
+            if kv_cache == "fp8":
+                raise ValueError("sliding_window with kv_cache=\"fp8\": the e4m3 decode attention kernel (bd_srv_decode_attention_kv8) has no "
+                                 "window yet; that kernel's window is the follow-up")
+        self.sliding_window = sliding_window
         if kv_cache == "fp8":
             if not ops.decode_attention_supported(cfg[3], cfg[4], hd_):
                 raise ValueError("kv_cache=\"fp8\" needs the HIP attention kernels: head_dim 128 and 1, 4 or 8 query heads per kv head")
@@ -600,15 +612,16 @@ class TenantDecoder(nn.Module):
     # ---------------------------------------------------------------- construction
     @classmethod
     def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
-                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None):
+                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None, sliding_window=None):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
-        (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope: as in __init__."""
+        (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope, sliding_window: as in
+        __init__."""
         cfg = MODEL_CONFIGS[name] if isinstance(name, str) else tuple(name)
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
         self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope, kv_cache=kv_cache,
-                   kv_scales=kv_scales)
+                   kv_scales=kv_scales, sliding_window=sliding_window)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -987,7 +1000,8 @@ class TenantDecoder(nn.Module):
             # a session's step: the same launch with each tenant at its own position; there is no stock-op form of it to fall to
             if not (S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd)):
                 raise RuntimeError("a ragged decode step needs the HIP decode attention (fast_glue, head_dim 128, 1 / 4 / 8 query heads per kv head)")
-            a = ops.decode_attention_ragged(qkv, self.cos, self.sin, ck, cv, cache["valid"], ragged[0], ragged[1], heads, kvh)
+            a = ops.decode_attention_ragged(qkv, self.cos, self.sin, ck, cv, cache["valid"], ragged[0], ragged[1], heads, kvh,
+                                            window=self.sliding_window)
         elif (cache.get("chunk") is not None and self.fast_glue and self.hip_prefill_attention and hd == 128 and qkv.is_contiguous()
               and not layer.qkv.interleave8):
             # a chunk of S rows at positions q0 .. q0 + S - 1 behind cached keys (prefill_chunk): RoPE of q and k at those positions + both cache
@@ -1001,10 +1015,10 @@ class TenantDecoder(nn.Module):
                 ops.rope_(qkv[..., :nq + nk], self.cos, self.sin, heads + kvh, S, q0)
                 ck[:, :, q0:q0 + S] = qkv[..., nq:nq + nk].view(T, S, kvh, hd).transpose(1, 2)
                 cv[:, :, q0:q0 + S] = qkv[..., nq + nk:].view(T, S, kvh, hd).transpose(1, 2)
-            a = ops.prefill_attention_cached(qkv[..., :nq].view(T, S, heads, hd), ck, cv, q0, kv_start=kvs)
+            a = ops.prefill_attention_cached(qkv[..., :nq].view(T, S, heads, hd), ck, cv, q0, kv_start=kvs, window=self.sliding_window)
         elif S == 1 and self.fast_glue and ops.decode_attention_supported(heads, kvh, hd):
             # decode: RoPE + cache append + attention over the valid keys in ONE launch (pos_idx is a one-element device tensor)
-            a = ops.decode_attention(qkv, self.cos, self.sin, ck, cv, cache["valid"], pos_idx, heads, kvh)
+            a = ops.decode_attention(qkv, self.cos, self.sin, ck, cv, cache["valid"], pos_idx, heads, kvh, window=self.sliding_window)
         elif (S > 1 and self.fast_glue and cache.get("kv_start") is not None and hd == 128 and S % 64 == 0 and qkv.is_contiguous()
               and not layer.qkv.interleave8):
             # prefill from position 0: in-place RoPE on the q and k slices of the fused projection output, flash-style attention over the
@@ -1014,10 +1028,10 @@ class TenantDecoder(nn.Module):
             k4, v4 = kf.view(T, S, kvh, hd), vf.view(T, S, kvh, hd)
             if short and ck.is_contiguous() and cv.is_contiguous():
                 ops.rope_kv_append_(qkv, self.cos, self.sin, ck, cv, heads, kvh, 0)       # RoPE of q and k + both cache writes: one launch
-                a = ops.prefill_attention(qf.view(T, S, heads, hd), k4, v4, kv_start=cache["kv_start"], causal=True)
+                a = ops.prefill_attention(qf.view(T, S, heads, hd), k4, v4, kv_start=cache["kv_start"], causal=True, window=self.sliding_window)
             else:
                 ops.rope_(qkv[..., :nq + nk], self.cos, self.sin, heads + kvh, S, 0)      # q and k heads: one launch
-                a = ops.prefill_attention(qf.view(T, S, heads, hd), k4, v4, kv_start=cache["kv_start"], causal=True)
+                a = ops.prefill_attention(qf.view(T, S, heads, hd), k4, v4, kv_start=cache["kv_start"], causal=True, window=self.sliding_window)
                 ck[:, :, :S] = k4.transpose(1, 2)
                 cv[:, :, :S] = v4.transpose(1, 2)
         else:
@@ -1115,6 +1129,13 @@ class TenantDecoder(nn.Module):
             am[t, L - len(p):] = True
         return ids.to(self.dev), am.to(self.dev)
 
+    def _band(self, mask, pos_idx, Lc):
+        """mask [T, 1, S, Lc] AND the sliding window's band: the query at pos_idx[s] keeps the keys > pos_idx[s] - W (its own included).  Device
+        arithmetic only (pos_idx may be the decode step's position tensor inside a captured graph); without a window the mask as it is."""
+        if self.sliding_window is None:
+            return mask
+        return mask & (torch.arange(Lc, device=self.dev)[None, :] > pos_idx[:, None] - self.sliding_window)[None, None]
+
     @torch.no_grad()
     def prefill(self, ids, attention_mask, cache, hidden=False):
         """hidden=True: every row of the residual stream after the last layer ([T, L, hidden], _hidden) instead of the last row's logits"""
@@ -1124,7 +1145,7 @@ class TenantDecoder(nn.Module):
         cache["valid"][:, :L] = attention_mask
         Lc = cache["k"][0].shape[2]
         causal = torch.ones(L, Lc, dtype=torch.bool, device=self.dev).tril()                     # query i sees keys <= i
-        mask = causal[None, None] & cache["valid"][:, None, None, :]
+        mask = self._band(causal[None, None] & cache["valid"][:, None, None, :], pos_idx, Lc)
         # fully masked query rows (left pads) would be NaN in softmax: let a pad see itself; its output is never used
         mask = mask | torch.eye(L, Lc, dtype=torch.bool, device=self.dev)[None, None]
         # left-padded prompts (prepare() builds them so): the HIP prefill attention takes the first valid key of each tenant instead of
@@ -1230,7 +1251,7 @@ class TenantDecoder(nn.Module):
         pos_idx = torch.arange(q0, q0 + n, device=self.dev)
         cache["valid"][:, q0:q0 + n] = True
         seen = torch.arange(Lc, device=self.dev)[None, :] <= pos_idx[:, None]                    # query i sees keys <= q0 + i
-        mask = seen[None, None] & cache["valid"][:, None, None, :]
+        mask = self._band(seen[None, None] & cache["valid"][:, None, None, :], pos_idx, Lc)
         cache["chunk"] = (q0, kv_start)
         try:
             return self.forward(ids, pos_idx, cache, mask)
@@ -1246,13 +1267,16 @@ class TenantDecoder(nn.Module):
             if "ticket" not in st:
                 st["ticket"] = torch.zeros(1, dtype=torch.int32, device=self.dev)      # (first call = outside any graph capture)
             x = ops.step_begin(self.embed, st["tok"], cache["valid"], st["pos"])
-            logits = self.forward(st["tok"], st["pos"], cache, cache["valid"][:, None, None, :], x=x)
+            mask = cache["valid"][:, None, None, :]
+            if not ops.decode_attention_supported(self.cfg[3], self.cfg[4], self.hd):       # (the stock-op attention arm alone reads the mask)
+                mask = self._band(mask, st["pos"], cache["valid"].shape[1])
+            logits = self.forward(st["tok"], st["pos"], cache, mask, x=x)
             if logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0:
                 ops.step_end(logits, st["tok"], st["out"], st["step"], st["pos"], st["stop_ids"], st["stopped"], st["ticket"])
                 return
         else:
             cache["valid"].index_fill_(1, st["pos"], True)
-            mask = cache["valid"][:, None, None, :]
+            mask = self._band(cache["valid"][:, None, None, :], st["pos"], cache["valid"].shape[1])
             logits = self.forward(st["tok"], st["pos"], cache, mask)
         nxt = torch.argmax(logits, dim=-1)
         st["tok"].copy_(nxt[:, None])
@@ -1338,7 +1362,7 @@ class TenantDecoder(nn.Module):
         v = views.get(t)
         if v is None:
             v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4,
-                              rope=self._rope[t], kv_cache=self.kv_cache)
+                              rope=self._rope[t], kv_cache=self.kv_cache, sliding_window=self.sliding_window)
             # the parent's table, or the tenant's rows of it: a slice of the storage load_tenant(rope=) rewrites in place
             v.cos, v.sin = (self.cos[t], self.sin[t]) if self.rope_per_tenant else (self.cos, self.sin)
             for layer in self.layers:

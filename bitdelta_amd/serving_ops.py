@@ -1,6 +1,8 @@
 """ctypes wrappers of the decode-step glue kernels (csrc/bd_serving.h): per-tenant RMSNorm, SwiGLU on the fused gate|up output,
 and single-token attention with RoPE + KV-cache append.  Callers of the hot path, used by serving_loop.TenantDecoder at decode;
 each has a stock-torch equivalent in that module (used at prefill and as the test reference)."""
+import operator
+
 import torch
 
 from ._lib import DTYPE_CODE, check, lib, ptr, require_gpu, stream_ptr, workspace
@@ -81,11 +83,20 @@ def table_stride(cos, sin, tenants):
     return cos.shape[1] * cos.shape[2]
 
 
-def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads):
+def _window(window):
+    """`window` as the *_window entries take it: an int >= 1 (W keys including the query's own), held to the C int range.  Host only."""
+    w = operator.index(window)
+    if w < 1:
+        raise ValueError("window = %d: a sliding window holds at least the query's own key" % w)
+    return min(w, 2 ** 31 - 1)
+
+
+def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads, window=None):
     """One new token per tenant.  qkv [T, 1, (heads + 2 kv_heads) * 128]; cos / sin [Lmax, 128], or contiguous [T, Lmax, 128]: tenant t's own
     tables (bd_srv_decode_attention_tab); caches [T, kv_heads, Lc, 128];
     valid [T, Lc] bool; pos: int64 device tensor with one element.  Returns [T, 1, heads * 128]; the caches and valid[:, pos] are
-    updated in place."""
+    updated in place.  window: None, or W >= 1: tenant t sees its valid keys pos - W + 1 .. pos only and the launch streams no other row
+    (bd_srv_decode_attention_window)."""
     T = qkv.shape[0]
     s_tab = table_stride(cos, sin, T)
     require_gpu(qkv, cos, sin, kcache, vcache, valid, pos)
@@ -99,6 +110,11 @@ def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads)
     # persistent per-stream scratch, zero-filled once: the kernel's arrival counters must be zero at launch and it restores them
     ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)
     with torch.cuda.device(qkv.device):
+        if window is not None:
+            check(L.bd_srv_decode_attention_window(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), None,
+                                                   ptr(out), T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
+                                                   DTYPE_CODE[qkv.dtype], _window(window), ptr(ws), need, stream_ptr()), "srv_decode_attention_window")
+            return out
         if cos.dim() == 3:
             check(L.bd_srv_decode_attention_tab(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(out),
                                                 T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
@@ -110,10 +126,10 @@ def decode_attention(qkv, cos, sin, kcache, vcache, valid, pos, heads, kv_heads)
     return out
 
 
-def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, heads, kv_heads):
+def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, heads, kv_heads, window=None):
     """decode_attention with one position per tenant: pos int64 [T], active bool [T] on the device.  Tenant t attends over its valid keys
     0 .. pos[t] and appends at pos[t]; a tenant that is inactive or whose position lies outside the cache gets a zero output row and its cache
-    and valid rows stay as they are.  cos / sin [Lmax, 128] or per tenant [T, Lmax, 128], as in decode_attention."""
+    and valid rows stay as they are.  cos / sin [Lmax, 128] or per tenant [T, Lmax, 128], and window, as in decode_attention."""
     T = qkv.shape[0]
     s_tab = table_stride(cos, sin, T)
     require_gpu(qkv, cos, sin, kcache, vcache, valid, pos, active)
@@ -127,6 +143,11 @@ def decode_attention_ragged(qkv, cos, sin, kcache, vcache, valid, pos, active, h
     need = L.bd_srv_decode_attention_workspace_bytes(T, heads, kv_heads, hd, kcache.shape[2])
     ws, need = workspace(need, qkv.device, zeroed=True) if need > 0 else (None, 0)          # (the scalar form's persistent scratch, same contract)
     with torch.cuda.device(qkv.device):
+        if window is not None:
+            check(L.bd_srv_decode_attention_window(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos), ptr(active),
+                                                   ptr(out), T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
+                                                   DTYPE_CODE[qkv.dtype], _window(window), ptr(ws), need, stream_ptr()), "srv_decode_attention_window")
+            return out
         if cos.dim() == 3:
             check(L.bd_srv_decode_attention_ragged_tab(ptr(qkv), ptr(cos), ptr(sin), s_tab, ptr(kcache), ptr(vcache), ptr(valid), ptr(pos),
                                                        ptr(active), ptr(out), T, heads, kv_heads, hd, kcache.shape[2], qkv.stride(0), out.stride(0),
@@ -149,10 +170,13 @@ def prefill_attention_supported(q, k, v):
     return k.shape == v.shape and k.shape[:2] == q.shape[:2] and k.dtype == q.dtype == v.dtype
 
 
-def prefill_attention(q, k, v, kv_start=None, causal=True, scale=None):
+def prefill_attention(q, k, v, kv_start=None, causal=True, scale=None, window=None):
     """Flash-style attention of a whole prompt.  q [B, S, heads, 128], k / v [B, S, kv_heads, 128] -- views into a fused q|k|v projection
     output are fine (after RoPE); kv_start: optional int32 [B] device tensor, first valid key of each sequence (left padding).
-    Returns [B, S, heads * 128] (what the o projection consumes)."""
+    Returns [B, S, heads * 128] (what the o projection consumes).  window: None, or W >= 1: query i sees keys max(kv_start, i - W + 1) .. i
+    (bd_srv_prefill_attention_window); a window is causal by definition, so causal=False with one is a ValueError."""
+    if window is not None and not causal:
+        raise ValueError("a sliding window is causal: causal=False with window=%r" % (window,))
     require_gpu(q, k, v)
     assert prefill_attention_supported(q, k, v), "prefill_attention: unsupported geometry"
     B, S, H, hd = q.shape
@@ -160,6 +184,13 @@ def prefill_attention(q, k, v, kv_start=None, causal=True, scale=None):
     if kv_start is not None:
         assert kv_start.dtype == torch.int32 and kv_start.is_cuda and kv_start.numel() == B and kv_start.is_contiguous()
     with torch.cuda.device(q.device):
+        if window is not None:
+            check(lib().bd_srv_prefill_attention_window(ptr(q), ptr(k), ptr(v), ptr(out), B, S, H, k.shape[2], hd, q.stride(0), q.stride(1),
+                                                        k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+                                                        ptr(kv_start) if kv_start is not None else None,
+                                                        float(scale if scale is not None else hd ** -0.5), _window(window),
+                                                        DTYPE_CODE[q.dtype], stream_ptr()), "srv_prefill_attention_window")
+            return out
         check(lib().bd_srv_prefill_attention(ptr(q), ptr(k), ptr(v), ptr(out), B, S, H, k.shape[2], hd, q.stride(0), q.stride(1),
                                              k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
                                              ptr(kv_start) if kv_start is not None else None,
@@ -182,11 +213,12 @@ def prefill_attention_cached_supported(q, kcache, vcache, q0=0):
             and 0 <= q0 and q0 + q.shape[1] <= kcache.shape[2])
 
 
-def prefill_attention_cached(q, kcache, vcache, q0, kv_start=None, scale=None):
+def prefill_attention_cached(q, kcache, vcache, q0, kv_start=None, scale=None, window=None):
     """Causal flash-style attention of a chunk of queries at positions q0 .. q0 + Sq - 1 over the keys in the KV caches (the chunk's own rows
     already appended: rope_kv_append_(..., pos0=q0)).  q [B, Sq, heads, 128] -- the q slice of a fused q|k|v projection output is fine;
     kcache / vcache [B, kv_heads, Lc, 128]; kv_start: optional int32 [B] device tensor, first valid key of each sequence (left padding).
-    Cache rows at or past q0 + Sq are not trusted.  Returns [B, Sq, heads * 128] (what the o projection consumes)."""
+    Cache rows at or past q0 + Sq are not trusted.  Returns [B, Sq, heads * 128] (what the o projection consumes).  window: as in
+    prefill_attention (bd_srv_prefill_attention_cached_window)."""
     require_gpu(q, kcache, vcache)
     q0 = int(q0)
     assert prefill_attention_cached_supported(q, kcache, vcache, q0), "prefill_attention_cached: unsupported geometry"
@@ -195,6 +227,14 @@ def prefill_attention_cached(q, kcache, vcache, q0, kv_start=None, scale=None):
     if kv_start is not None:
         assert kv_start.dtype == torch.int32 and kv_start.is_cuda and kv_start.numel() == B and kv_start.is_contiguous()
     with torch.cuda.device(q.device):
+        if window is not None:
+            check(lib().bd_srv_prefill_attention_cached_window(ptr(q), ptr(kcache), ptr(vcache), ptr(out), B, Sq, H, kcache.shape[1], hd, q0,
+                                                               kcache.shape[2], q.stride(0), q.stride(1), kcache.stride(0), kcache.stride(1),
+                                                               kcache.stride(2), vcache.stride(0), vcache.stride(1), vcache.stride(2), out.stride(0),
+                                                               out.stride(1), ptr(kv_start) if kv_start is not None else None,
+                                                               float(scale if scale is not None else hd ** -0.5), _window(window),
+                                                               DTYPE_CODE[q.dtype], stream_ptr()), "srv_prefill_attention_cached_window")
+            return out
         check(lib().bd_srv_prefill_attention_cached(ptr(q), ptr(kcache), ptr(vcache), ptr(out), B, Sq, H, kcache.shape[1], hd, q0, kcache.shape[2],
                                                     q.stride(0), q.stride(1), kcache.stride(0), kcache.stride(1), kcache.stride(2),
                                                     vcache.stride(0), vcache.stride(1), vcache.stride(2), out.stride(0), out.stride(1),

@@ -679,6 +679,36 @@ int bd_srv_prefill_attention_cached(const void* Q, const void* Kc, const void* V
  * back to zero, so a buffer that is zero-filled once and used by one stream at a time can be reused by every call. */
 int64_t bd_srv_decode_attention_workspace_bytes(int T, int H, int KVH, int head_dim, int Lc);
 
+/* ---- Sliding-window attention (serving_loop.TenantDecoder(sliding_window=W); Mistral-7B-v0.1 and its fine-tunes were trained with 4096).
+ * DEFINITION.  window = W, an integer >= 1.  The query at cache position i sees key j iff
+ *     j <= i   and   i - j < W   and   j >= kv_start (the prefill forms)   and   valid[j] != 0 (decode)
+ *   -- W keys INCLUDING the query's own.  This is Mistral's reference implementation and the mask of current `transformers`
+ *   (kv_idx > q_idx - sliding_window); older `transformers` releases let W + 1 keys through, which these entries do not reproduce.  Positions
+ *   are cache positions: valid keys are contiguous behind the left pads, so index distance is token distance.  The cache stays linear (Lc
+ *   rows); the window bounds what a launch READS: decode streams min(pos + 1, W) rows per (tenant, kv head), a 128-query prefill block visits
+ *   at most (W + 128) / 64 + 1 key tiles.  With W >= the key range each entry is bit for bit its un-windowed entry.
+ * bd_srv_decode_attention_window: ONE entry for the four 16-bit decode forms.  active == NULL: the lockstep form, pos is one device scalar;
+ *   otherwise pos [T] and active [T] bytes with bd_srv_decode_attention_ragged's stay-out rule.  s_tab == 0: one shared table pair (no
+ *   alignment asked of it); otherwise the *_tab entries' per-tenant tables and their checks.  Validation as in those entries, in their
+ *   order; window < 1 -> BD_E_BAD_SHAPE with the first shape checks (in front of the dtype check and of the empty call T == 0), all
+ *   before any device call.  The append at pos, the valid mark, the workspace
+ *   (bd_srv_decode_attention_workspace_bytes: sized by Lc as before) and its ticket contract are theirs.  Split rule and ring depth take the
+ *   rows a launch can hold, min(Lc, W), in place of Lc, and the splits share the window [max(0, pos + 1 - W), pos]; a split past it is empty.
+ *   The windowed kernels merge with the 16-split body at every split count: bd_last_attention_form() afterwards reports MAXS = 16.
+ * bd_srv_prefill_attention_window / bd_srv_prefill_attention_cached_window: bd_srv_prefill_attention (always causal: there is no `causal`
+ *   argument) and bd_srv_prefill_attention_cached with `window` behind `scale`; their checks, window < 1 -> BD_E_BAD_SHAPE with the first of them.  Row i of the
+ *   cached form is bit for bit row q0 + i of the whole-prompt form at the same W. */
+int bd_srv_decode_attention_window(const void* QKV, const void* cos_t, const void* sin_t, int64_t s_tab, void* kcache, void* vcache, void* valid,
+                                   const int64_t* pos, const void* active, void* out, int T, int H, int KVH, int head_dim, int Lc,
+                                   int64_t s_qkv, int64_t s_out, int dtype, int window, void* ws, int64_t ws_bytes, void* stream);
+int bd_srv_prefill_attention_window(const void* Q, const void* K, const void* V, void* O, int B, int S, int H, int KVH, int head_dim,
+                                    int64_t sqb, int64_t sqs, int64_t skb, int64_t sks, int64_t svb, int64_t svs, int64_t sob, int64_t sos,
+                                    const int32_t* kv_start, float scale, int window, int dtype, void* stream);
+int bd_srv_prefill_attention_cached_window(const void* Q, const void* Kc, const void* Vc, void* O, int B, int Sq, int H, int KVH, int head_dim,
+                                           int q0, int Lc, int64_t sqb, int64_t sqs, int64_t skb, int64_t skh, int64_t sks, int64_t svb,
+                                           int64_t svh, int64_t svs, int64_t sob, int64_t sos, const int32_t* kv_start, float scale, int window,
+                                           int dtype, void* stream);
+
 /* ---- The KV cache in 8 bits (serving_loop.TenantDecoder(kv_cache="fp8"); kernels in csrc/bd_attn_kv8.h).  DEFINITION, which the tests hold the
  * kernels to:
  * Format.  OCP e4m3fn: 1 sign, 4 exponent bits (bias 7), 3 mantissa bits; largest finite value 448; no infinity; 0x7f / 0xff = NaN.  The caches
