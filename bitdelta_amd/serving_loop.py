@@ -1733,6 +1733,11 @@ def truncation_params(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0
 
 NO_TRUNCATION = truncation_params()
 
+# One request as TenantSession._request validates it: the sorted stop ids, then the six features' values (con: a TokenAutomaton or None; ss:
+# TenantSession._stop_sequences_arg's value).  _NO_REQUEST is what load_tenant leaves in a slot.
+_Request = collections.namedtuple("_Request", "stops sp pp con ss bp tp")
+_NO_REQUEST = _Request([], GREEDY, NEUTRAL, None, None, NO_BANS, NO_TRUNCATION)
+
 
 class TenantSession:
     """Per-tenant requests on one TenantDecoder: a tenant is admitted when its request arrives (`submit`) and retires at its own stop token, its
@@ -1832,34 +1837,28 @@ class TenantSession:
                  max_constraint_states=256, max_constraint_edges=4096, stop_sequences=False, max_stop_sequences=4, max_stop_sequence_len=8,
                  bans=False, max_bad_words=16, max_bad_word_len=8, truncation=False):
         self.logprobs = logprobs_count(logprobs)
-        self.truncation = bool(truncation)
-        if self.truncation and not sampling:
+        self.sampling, self.penalties, self.constraints = bool(sampling), bool(penalties), bool(constraints)
+        self.stop_sequences, self.bans, self.truncation = bool(stop_sequences), bool(bans), bool(truncation)
+        if self.truncation and not self.sampling:
             raise ValueError("truncation=True cuts the tail of a sampled distribution: make the session with sampling=True as well")
-        self.penalties = bool(penalties)
-        self.constraints = bool(constraints)
-        self.stop_sequences = bool(stop_sequences)
+
+        def sizes(lo, *args):                         # a feature's size arguments: (value, name, largest) each
+            for v, what, top in args:
+                if not (isinstance(v, int) and not isinstance(v, bool) and lo <= v <= top):
+                    raise ValueError("%s = %r: an integer %d .. %d is required" % (what, v, lo, top))
         if self.stop_sequences:
-            for v, what, top in ((max_stop_sequences, "max_stop_sequences", ops.STOP_SEQ_MAX),
-                                 (max_stop_sequence_len, "max_stop_sequence_len", ops.STOP_SEQ_LEN_MAX)):
-                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
-                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
-        self.bans = bool(bans)
+            sizes(1, (max_stop_sequences, "max_stop_sequences", ops.STOP_SEQ_MAX), (max_stop_sequence_len, "max_stop_sequence_len", ops.STOP_SEQ_LEN_MAX))
         if self.bans:
-            for v, what, top in ((max_bad_words, "max_bad_words", ops.BAN_WORDS_MAX), (max_bad_word_len, "max_bad_word_len", ops.BAN_WORD_LEN_MAX)):
-                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
-                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
+            sizes(1, (max_bad_words, "max_bad_words", ops.BAN_WORDS_MAX), (max_bad_word_len, "max_bad_word_len", ops.BAN_WORD_LEN_MAX))
             if max(int(max_stop_ids), 1) > ops.BAN_STOP_MAX:
                 raise ValueError("a session with bans holds at most %d stop ids per request" % ops.BAN_STOP_MAX)
         if self.constraints:
-            for v, what, top in ((max_constraint_states, "max_constraint_states", ops.CONSTRAINT_STATES_MAX),
-                                 (max_constraint_edges, "max_constraint_edges", ops.CONSTRAINT_EDGES_MAX)):
-                if not (isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top):
-                    raise ValueError("%s = %r: an integer 1 .. %d is required" % (what, v, top))
+            sizes(1, (max_constraint_states, "max_constraint_states", ops.CONSTRAINT_STATES_MAX),
+                  (max_constraint_edges, "max_constraint_edges", ops.CONSTRAINT_EDGES_MAX))
             if max(int(max_stop_ids), 1) > ops.CONSTRAINT_STOP_MAX:
                 raise ValueError("a session with constraints holds at most %d stop ids per request" % ops.CONSTRAINT_STOP_MAX)
-        if self.penalties and not (isinstance(max_logit_bias, int) and not isinstance(max_logit_bias, bool)
-                                   and 0 <= max_logit_bias <= ops.LOGIT_BIAS_MAX):
-            raise ValueError("max_logit_bias = %r: an integer 0 .. %d is required" % (max_logit_bias, ops.LOGIT_BIAS_MAX))
+        if self.penalties:
+            sizes(0, (max_logit_bias, "max_logit_bias", ops.LOGIT_BIAS_MAX))
         _, _, _, heads, kvh, _ = dec.cfg
         if not (dec.fast_glue and dec.step_kernels):
             raise ValueError("a session runs on the HIP glue and step kernels (fast_glue, step_kernels); there is no stock-op ragged step")
@@ -1883,34 +1882,135 @@ class TenantSession:
         self.done = torch.zeros(T, dtype=torch.uint8, device=dev)
         self.stop_ids = torch.full((T, max(int(max_stop_ids), 1)), -1, dtype=torch.long, device=dev)
         self.out = torch.zeros(T, dec.max_len, dtype=torch.long, device=dev)      # (a caller may swap in a strided view BEFORE the first step)
-        self.sampling = bool(sampling)
-        if self.sampling:
+        self._first_lp = None           # the first tokens' entries between _first_tokens and the end of _admit (device tensors)
+        self._graphs = {}
+        self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
+        dec._sessions.add(self)
+        # The request features as STAGES.  One set-up block per enabled feature, in launch order, allocates the feature's arrays and appends its
+        # entries to these lists; admission, the step, the trial-step state, the graph key and load_tenant loop over them.  Every entry takes the
+        # session as its first argument instead of closing over it: a session holds no reference cycle, so its arrays and captured graphs go when
+        # the last reference does.  Every launch is `ops.<name>`, looked up when it is made.
+        self._writes = []     # write(s, t, req, context, history, fold): the record's values for tenant t, before the first token is chosen
+        self._masks = []      # (rows(s, logits, rows), step(s, logits)): the masks between the lm_head and the choice; each reads the one before
+        self._after = []      # (rows(s, raw, tok) or None, step(s, raw)): behind the choice; None: the host makes the first one, in its _admits entry
+        self._admits = []     # admit(s, t, req, first, row) -> reason bits: the feature's part of admission once the first token is known
+        self._trial = []      # the tensors a trial step must put back (_state)
+        self._key = ()        # what the graph key gains
+        self._clears = []     # clear(s, t): load_tenant's reset of slot t
+        V, ldt = dec.lm_head.shape[-2], dec.lm_head.dtype
+        put = lambda v, dtype: torch.tensor(v, dtype=dtype).to(dev)
+        if self.sampling:                             # per tenant: the parameters the step end (step_end_sample) and the first draw read
             self.temperature = torch.zeros(T, dtype=torch.float32, device=dev)
             self.top_k = torch.zeros(T, dtype=torch.int32, device=dev)
             self.top_p = torch.ones(T, dtype=torch.float32, device=dev)
             self.seed = torch.zeros(T, dtype=torch.long, device=dev)          # the seed's 64 bits
+
+            def write_sampling(s, t, req, *_):
+                tau, k, p, s_ = req.sp
+                s.temperature[t] = tau
+                s.top_k[t] = min(k, 2 ** 31 - 1)
+                s.top_p[t] = p
+                s.seed[t] = s_ - (1 << 64) if s_ >= 1 << 63 else s_
+            self._writes.append(write_sampling)
+            self._clears.append(lambda s, t: write_sampling(s, t, _NO_REQUEST))
         if self.logprobs is not None:                 # entry [t, j] belongs to out[t, j]; entries at or past n[t] are unspecified
             cap, k = self.out.shape[1], self.logprobs
             self.lp_n = torch.zeros(T, dtype=torch.long, device=dev)          # step_logprobs' own counter: follows n
             self.lp = torch.zeros(T, cap, dtype=torch.float32, device=dev)
             self.top_id = torch.zeros(T, cap, k, dtype=torch.int32, device=dev)
             self.top_lp = torch.zeros(T, cap, k, dtype=torch.float32, device=dev)
+
+            def first_logprobs(s, raw, tok):          # the first tokens' entries from the prefill's RAW rows and the tokens just chosen; no host read
+                s._first_lp = ops.token_logprobs(raw, tok.view(-1), s.logprobs)
+
+            def admit_logprobs(s, t, req, first, row):      # the turn's entries restart with it, as result() does
+                lp, top_id, top_lp = s._first_lp
+                s.lp[t, 0] = lp[row]
+                s.top_id[t, 0] = top_id[row]
+                s.top_lp[t, 0] = top_lp[row]
+                s.lp_n[t] = 1
+                return 0
+            self._after.append((first_logprobs, lambda s, raw: ops.step_logprobs(raw, s.tok, s.n, s.lp_n, s.lp, s.top_id, s.top_lp)))
+            self._admits.append(admit_logprobs)
+            self._trial += [self.lp_n]
+
+            def clear_logprobs(s, t):
+                s.lp_n[t] = 0
+            self._clears.append(clear_logprobs)
         if self.penalties:                            # per tenant: token history, (r, 1 / r, presence, frequency), the bias list, the penalised row
-            V = dec.lm_head.shape[-2]
             self.hist = torch.zeros(T, V, dtype=torch.int16, device=dev)
             self.pen = torch.tensor([penalty_row(NEUTRAL)] * T, dtype=torch.float32).to(dev)
             self.bias_id = torch.full((T, max_logit_bias), -1, dtype=torch.int32, device=dev)
             self.bias_val = torch.zeros(T, max_logit_bias, dtype=torch.float32, device=dev)
-            self.plogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+            self.plogits = torch.zeros(T, V, dtype=ldt, device=dev)
+
+            def write_penalties(s, t, req, context, history, fold):
+                # the parameters, and the history: cleared (submit) or folded (extend: fold_history), then bit 15 set at `context`
+                cap, bias = s.bias_id.shape[1], req.pp[3]
+                s.pen[t] = put(penalty_row(req.pp), torch.float32)
+                if cap:
+                    s.bias_id[t] = put([b[0] for b in bias] + [-1] * (cap - len(bias)), torch.int32)
+                    s.bias_val[t] = put([b[1] for b in bias] + [0.0] * (cap - len(bias)), torch.float32)
+                if fold:
+                    s.hist[t] = fold_history(s.hist[t])
+                else:
+                    s.hist[t].zero_()
+                if len(context):
+                    s.hist[t].index_fill_(0, put(context, torch.long), -32768)
+            self._writes.append(write_penalties)
+            # the step form counts the token fed in and writes the row the step end chooses from
+            self._masks.append((lambda s, logits, rows: ops.penalize_rows(logits, s.hist[rows], s.pen[rows], s.bias_id[rows], s.bias_val[rows]),
+                                lambda s, logits: ops.step_penalize(logits, s.plogits, s.hist, s.tok, s.active_flags, s.pen, s.bias_id, s.bias_val)))
+            self._trial += [self.hist]                # (the warm-up and the capture step would count their token twice otherwise)
+            self._clears.append(lambda s, t: write_penalties(s, t, _NO_REQUEST, (), (), False))
         if self.constraints:                          # per tenant: the automaton at the session's sizes, its state, the advance launch's counter, the masked row
-            V, S, E = dec.lm_head.shape[-2], max_constraint_states, max_constraint_edges
+            S, E = max_constraint_states, max_constraint_edges
             self.c_state = torch.full((T,), -1, dtype=torch.int32, device=dev)
             self.c_n = torch.zeros(T, dtype=torch.long, device=dev)           # step_constrain_advance's own counter: follows n
             self.c_off = torch.zeros(T, S + 1, dtype=torch.int32, device=dev)
             self.c_tok = torch.zeros(T, E, dtype=torch.int32, device=dev)
             self.c_next = torch.zeros(T, E, dtype=torch.int32, device=dev)
             self.c_acc = torch.zeros(T, S, dtype=torch.uint8, device=dev)
-            self.clogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+            self.clogits = torch.zeros(T, V, dtype=ldt, device=dev)
+
+            def write_constraint(s, t, req, *_):
+                # the automaton into tenant t's slices (the rest of them is never indexed: every offset and target lies inside what is
+                # written) and the start state, or -1
+                con = req.con
+                if con is None:
+                    s.c_state[t] = -1
+                    return
+                S, E = con.n_states, con.n_edges
+                s.c_off[t, :S + 1] = put(con.off, torch.int32)
+                if E:
+                    s.c_tok[t, :E] = put(con.edge_tok, torch.int32)
+                    s.c_next[t, :E] = put(con.edge_next, torch.int32)
+                s.c_acc[t, :S] = put(con.accepting, torch.uint8)
+                s.c_state[t] = 0
+
+            def admit_constraint(s, t, req, first, row):    # the automaton is advanced once, on the host, with the first token
+                s.c_n[t] = 1
+                if req.con is None:
+                    return 0
+                state = req.con.step(0, first)
+                s.c_state[t] = state
+                return 8 if req.con.is_final(state) else 0
+
+            def clear_constraint(s, t):
+                s.c_state[t] = -1
+                s.c_n[t] = 0
+            self._writes.append(write_constraint)
+            # masks the (penalised) row by each tenant's automaton state; the state itself moves behind the step end
+            self._masks.append((
+                lambda s, logits, rows: ops.constrain_rows(logits, s.c_state[rows].contiguous(), s.c_off[rows].contiguous(), s.c_tok[rows].contiguous(),
+                                                           s.c_acc[rows].contiguous(), s.stop_ids[rows].contiguous()),
+                lambda s, logits: ops.step_constrain(logits, s.clogits, s.c_state, s.c_off, s.c_tok, s.c_acc, s.stop_ids, s.active_flags)))
+            # follows the token just chosen; a tenant that reaches a final state retires here (reason 8)
+            self._after.append((None, lambda s, raw: ops.step_constrain_advance(s.tok, s.n, s.c_n, s.c_state, s.c_off, s.c_tok, s.c_next, s.c_acc,
+                                                                                s.active_flags, s.done)))
+            self._admits.append(admit_constraint)
+            self._trial += [self.c_state, self.c_n]   # (... and would advance twice)
+            self._clears.append(clear_constraint)
         if self.stop_sequences:                       # per tenant: the table at the session's sizes, the launch's counter, its two results
             Q, W = max_stop_sequences, max_stop_sequence_len
             self.ss_tok = torch.full((T, Q, W), -1, dtype=torch.int32, device=dev)
@@ -1918,23 +2018,81 @@ class TenantSession:
             self.ss_n = torch.zeros(T, dtype=torch.long, device=dev)          # step_stop_sequences' own counter: follows n
             self.hit = torch.full((T,), -1, dtype=torch.int32, device=dev)
             self.hold = torch.zeros(T, dtype=torch.int32, device=dev)
+
+            def write_stop_sequences(s, t, req, *_):        # the table rows (_stop_sequences_arg's)
+                tok, lens = req.ss[1]
+                s.ss_tok[t] = put(tok, torch.int32)
+                s.ss_len[t] = put(lens, torch.int32)
+
+            def admit_stop_sequences(s, t, req, first, row):
+                # the rule of the launch for n = 1, on the host: a one-token sequence equal to the first token is a hit
+                hit, hold = stop_sequence_scan([first], req.ss[0])
+                s.hit[t], s.hold[t], s.ss_n[t] = hit, hold, 1
+                return 16 if hit >= 0 else 0
+
+            def clear_stop_sequences(s, t):
+                s.ss_tok[t].fill_(-1)
+                s.ss_len[t].zero_()
+                s.hit[t], s.hold[t], s.ss_n[t] = -1, 0, 0
+            self._writes.append(write_stop_sequences)
+            # LAST: a turn that now ends with one of its sequences retires here (reason 16, OR-ed)
+            self._after.append((None, lambda s, raw: ops.step_stop_sequences(s.out, s.n, s.ss_n, s.ss_tok, s.ss_len, s.hit, s.hold, s.active_flags,
+                                                                             s.done)))
+            self._admits.append(admit_stop_sequences)
+            self._trial += [self.ss_n, self.hit, self.hold]       # (... and would leave a hit of the trial steps behind)
+            self._key += (True, Q, W)
+            self._clears.append(clear_stop_sequences)
         if self.bans:                                 # per tenant: the conversation's real tokens, the three parameters at the session's sizes, the masked row
-            V, Q, W = dec.lm_head.shape[-2], max_bad_words, max_bad_word_len
+            Q, W = max_bad_words, max_bad_word_len
             self.ctx = torch.zeros(T, self.Lc, dtype=torch.int32, device=dev)
             self.ctx_len = torch.zeros(T, dtype=torch.int32, device=dev)
             self.ban_ngram = torch.zeros(T, dtype=torch.int32, device=dev)
             self.ban_tok = torch.full((T, Q, W), -1, dtype=torch.int32, device=dev)
             self.ban_len = torch.zeros(T, Q, dtype=torch.int32, device=dev)
             self.ban_min = torch.zeros(T, dtype=torch.int32, device=dev)
-            self.blogits = torch.zeros(T, V, dtype=dec.lm_head.dtype, device=dev)
+            self.blogits = torch.zeros(T, V, dtype=ldt, device=dev)
             self._ctx_tokens = [[] for _ in range(T)]  # the host's copy of ctx[t, :ctx_len[t]]: extend appends to it
+
+            def write_bans(s, t, req, context, history, fold):
+                # the conversation so far (`history`: ALL its real tokens up to this turn; the host keeps the list) and the three parameters
+                tokens = [int(i) for i in history]
+                s._ctx_tokens[t] = tokens
+                if tokens:
+                    s.ctx[t, :len(tokens)] = put(tokens, torch.int32)
+                s.ctx_len[t] = len(tokens)
+                g, words, lo = req.bp
+                tok, lens = ban_word_table(words, s.ban_tok.shape[1], s.ban_tok.shape[2])
+                s.ban_ngram[t] = g
+                s.ban_tok[t] = put(tok, torch.int32)
+                s.ban_len[t] = put(lens, torch.int32)
+                s.ban_min[t] = lo
+
+            def clear_bans(s, t):
+                write_bans(s, t, _NO_REQUEST, (), (), False)
+                s.stop_ids[t].fill_(-1)               # (the stop ids min_new_tokens held back)
+            self._writes.append(write_bans)
+            # masks what the tenant's own history forbids; wins over a positive bias and a constraint's edge.  The rows form passes no n: the
+            # turn has no token yet, so min_new_tokens > 0 holds back the stop ids there too.  The launch keeps no counter: nothing to put back
+            self._masks.append((lambda s, logits, rows: ops.ban_rows(logits, s.ctx[rows].contiguous(), s.ctx_len[rows].contiguous(),
+                                                                     s.ban_ngram[rows].contiguous(), s.ban_tok[rows].contiguous(),
+                                                                     s.ban_len[rows].contiguous(), s.ban_min[rows].contiguous(),
+                                                                     s.stop_ids[rows].contiguous()),
+                                lambda s, logits: ops.step_ban(logits, s.blogits, s.ctx, s.ctx_len, s.out, s.n, s.ban_ngram, s.ban_tok, s.ban_len,
+                                                               s.ban_min, s.stop_ids, s.active_flags)))
+            self._key += ("bans", Q, W)
+            self._clears.append(clear_bans)
         if self.truncation:                           # per tenant: (min_p, typical_p, epsilon_cutoff, eta_cutoff), and the truncated row
             self.trunc = torch.tensor([NO_TRUNCATION] * T, dtype=torch.float32).to(dev)
-            self.tlogits = torch.zeros(T, dec.lm_head.shape[-2], dtype=dec.lm_head.dtype, device=dev)
-        self._first_lp = None           # the first tokens' entries between _first_tokens and _admit (device tensors)
-        self._graphs = {}
-        self._kv_start = [None] * T     # per tenant: the first cache row of its conversation (left pads of its first prompt); None = nothing to extend
-        dec._sessions.add(self)
+            self.tlogits = torch.zeros(T, V, dtype=ldt, device=dev)
+
+            def write_truncation(s, t, req, *_):
+                s.trunc[t] = put(req.tp, torch.float32)
+            self._writes.append(write_truncation)
+            # the last of the masks: cuts the tail of the row the others leave, at the tenant's own temperature
+            self._masks.append((lambda s, logits, rows: ops.truncate_rows(logits, s.temperature[rows].contiguous(), s.trunc[rows].contiguous()),
+                                lambda s, logits: ops.step_truncate(logits, s.tlogits, s.temperature, s.trunc, s.active_flags)))
+            self._key += ("truncation",)
+            self._clears.append(lambda s, t: write_truncation(s, t, _NO_REQUEST))
 
     # ------------------------------------------------------------ admission
     @torch.no_grad()
@@ -1960,22 +2118,8 @@ class TenantSession:
         self.done[t] = 0
         self.n[t] = 0
         self.out[t].zero_()
-        if self.logprobs is not None:
-            self.lp_n[t] = 0
-        if self.sampling:
-            self._write_params(t, GREEDY)
-        if self.penalties:
-            self.hist[t].zero_()
-            self._write_penalties(t, NEUTRAL)
-        if self.constraints:
-            self.c_state[t] = -1
-            self.c_n[t] = 0
-        if self.stop_sequences:
-            self._write_stop_sequences(t, self._stop_sequences_arg(()), -1, 0, 0)
-        if self.bans:
-            self._write_bans(t, NO_BANS, [], [])
-        if self.truncation:
-            self._write_truncation(t, NO_TRUNCATION)
+        for clear in self._clears:
+            clear(self, t)
         return rescaled
 
     def _params(self, temperature, top_k, top_p, seed):
@@ -2034,11 +2178,6 @@ class TenantSession:
                              "epsilon_cutoff / eta_cutoff")
         return tp
 
-    def _write_truncation(self, t, tp):
-        """a truncation session, before the first token is chosen: tenant t's four numbers.  One torch op on the current stream, no host read."""
-        if self.truncation:
-            self.trunc[t] = torch.tensor(tp, dtype=torch.float32).to(self.dec.dev)
-
     def _per_tenant_bad_words(self, v):
         """submit_all's bad_words=: one list of token-id lists for all tenants, or a list with one such list per tenant, told apart by depth as
         _per_tenant_stop_sequences tells stop sequences apart"""
@@ -2048,28 +2187,6 @@ class TenantSession:
         """a ban session keeps the conversation's real tokens as int32, at most one per cache row"""
         if self.bans and not (len(tokens) <= self.Lc and all(-2 ** 31 <= int(i) < 2 ** 31 for i in tokens)):
             raise ValueError("the conversation does not fit the ban history (%d tokens, int32 ids)" % self.Lc)
-
-    def _write_bans(self, t, bp, tokens, stops):
-        """a ban session, before the first token is chosen: tenant t's conversation so far (`tokens`: ALL its real tokens up to this turn; the
-        host keeps the list), its three parameters, and the stop ids min_new_tokens holds back.  Torch ops on the current stream, no host
-        read."""
-        if not self.bans:
-            return
-        dev = self.dec.dev
-        tokens = [int(i) for i in tokens]
-        self._ctx_tokens[t] = tokens
-        if tokens:
-            self.ctx[t, :len(tokens)] = torch.tensor(tokens, dtype=torch.int32).to(dev)
-        self.ctx_len[t] = len(tokens)
-        g, words, lo = bp
-        tok, lens = ban_word_table(words, self.ban_tok.shape[1], self.ban_tok.shape[2])
-        self.ban_ngram[t] = g
-        self.ban_tok[t] = torch.tensor(tok, dtype=torch.int32).to(dev)
-        self.ban_len[t] = torch.tensor(lens, dtype=torch.int32).to(dev)
-        self.ban_min[t] = lo
-        self.stop_ids[t].fill_(-1)                    # (_admit writes the same values again)
-        if stops:
-            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long).to(dev)
 
     def _per_tenant_stop_sequences(self, v):
         """submit_all's stop_sequences=: one list of token-id lists for all tenants, or a list with one such list per tenant.  The two are told
@@ -2084,64 +2201,11 @@ class TenantSession:
             return list(v)
         return [v] * self.T
 
-    def _write_stop_sequences(self, t, ss, hit, hold, n):
-        """a stop-sequence session: tenant t's table rows (_stop_sequences_arg's), results and counter.  Torch ops on the current stream, no host
-        read."""
-        dev = self.dec.dev
-        tok, lens = ss[1]
-        self.ss_tok[t] = torch.tensor(tok, dtype=torch.int32).to(dev)
-        self.ss_len[t] = torch.tensor(lens, dtype=torch.int32).to(dev)
-        self.hit[t] = hit
-        self.hold[t] = hold
-        self.ss_n[t] = n
-
     def _check_constraint(self, con, stops):
         """the checks that need the session's sizes and the request's stop ids (TokenAutomaton.check), before anything is touched"""
         if con is not None:
             con.check(self.dec.lm_head.shape[-2], self.c_acc.shape[1], self.c_tok.shape[1], bool(stops))
         return con
-
-    def _write_constraint(self, t, con, stops):
-        """a constraint session, before the first token is chosen: the automaton into tenant t's slices (the rest of them is never indexed: every
-        offset and target lies inside what is written), the start state or -1, and the stop ids the start state may allow.  Torch ops on the
-        current stream, no host read."""
-        if not self.constraints:
-            return
-        dev = self.dec.dev
-        self.stop_ids[t].fill_(-1)                    # (_admit writes the same values again)
-        if stops:
-            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long).to(dev)
-        if con is None:
-            self.c_state[t] = -1
-            return
-        S, E = con.n_states, con.n_edges
-        self.c_off[t, :S + 1] = torch.tensor(con.off, dtype=torch.int32).to(dev)
-        if E:
-            self.c_tok[t, :E] = torch.tensor(con.edge_tok, dtype=torch.int32).to(dev)
-            self.c_next[t, :E] = torch.tensor(con.edge_next, dtype=torch.int32).to(dev)
-        self.c_acc[t, :S] = torch.tensor(con.accepting, dtype=torch.uint8).to(dev)
-        self.c_state[t] = 0
-
-    def _write_penalties(self, t, pp):
-        cap = self.bias_id.shape[1]
-        self.pen[t] = torch.tensor(penalty_row(pp), dtype=torch.float32).to(self.dec.dev)
-        if cap:
-            bias = pp[3]
-            self.bias_id[t] = torch.tensor([b[0] for b in bias] + [-1] * (cap - len(bias)), dtype=torch.int32).to(self.dec.dev)
-            self.bias_val[t] = torch.tensor([b[1] for b in bias] + [0.0] * (cap - len(bias)), dtype=torch.float32).to(self.dec.dev)
-
-    def _context(self, t, tokens, pp, fold=False):
-        """a penalty session, before the first token is chosen: tenant t's parameters, and its history -- cleared (submit) or folded (extend:
-        fold_history), then bit 15 set at `tokens`, the real tokens this admission adds to the context.  Torch ops on the current stream, no
-        host read."""
-        if not self.penalties:
-            return
-        self._write_penalties(t, pp)
-        if fold:
-            self.hist[t] = fold_history(self.hist[t])
-        else:
-            self.hist[t].zero_()
-        self.hist[t].index_fill_(0, torch.tensor(tokens, dtype=torch.long).to(self.dec.dev), -32768)
 
     def _check_tokens(self, tokens):
         """a penalty session indexes its history with the request's tokens: ids outside the vocabulary are refused on the host"""
@@ -2157,92 +2221,73 @@ class TenantSession:
             return list(v)
         return [v] * self.T
 
-    def _write_params(self, t, sp):
-        tau, k, p, s_ = sp
-        self.temperature[t] = tau
-        self.top_k[t] = min(k, 2 ** 31 - 1)
-        self.top_p[t] = p
-        self.seed[t] = s_ - (1 << 64) if s_ >= 1 << 63 else s_
-
-    def _first_tokens(self, logits, sps, d, rows=slice(None)):
-        """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
-        cache row the token will occupy.  One host read, the one admission makes anyway.  rows: the tenants the R rows belong to; a penalty
-        session chooses from their penalised rows (serving_ops.penalize_rows on the history and parameters _context has just written), a
-        constraint session from those rows masked by the start states _write_constraint has just written (serving_ops.constrain_rows), and
-        the log-probabilities are still the raw rows'."""
-        raw = logits
-        if self.penalties:
-            logits = ops.penalize_rows(logits, self.hist[rows], self.pen[rows], self.bias_id[rows], self.bias_val[rows])
-        if self.constraints:
-            logits = ops.constrain_rows(logits, self.c_state[rows].contiguous(), self.c_off[rows].contiguous(), self.c_tok[rows].contiguous(),
-                                        self.c_acc[rows].contiguous(), self.stop_ids[rows].contiguous())
-        if self.bans:                                 # n absent: the turn has no token yet, so min_new_tokens > 0 holds back the stop ids here too
-            logits = ops.ban_rows(logits, self.ctx[rows].contiguous(), self.ctx_len[rows].contiguous(), self.ban_ngram[rows].contiguous(),
-                                  self.ban_tok[rows].contiguous(), self.ban_len[rows].contiguous(), self.ban_min[rows].contiguous(),
-                                  self.stop_ids[rows].contiguous())
-        if not self.sampling:
-            tok = torch.argmax(logits, dim=-1)
-            self._keep_first_logprobs(raw, tok)
-            return tok.tolist()
-        dev = self.dec.dev
-        if self.truncation:                           # the last of the masks, at the request's own temperature (_admit writes it to the device later)
-            logits = ops.truncate_rows(logits, torch.tensor([sp[0] for sp in sps], dtype=torch.float32).to(dev), self.trunc[rows].contiguous())
-        if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
-            logits = logits.contiguous()
-        tok = ops.sample_rows(logits, torch.tensor([sp[0] for sp in sps], dtype=torch.float32).to(dev),
-                              torch.tensor([min(sp[1], 2 ** 31 - 1) for sp in sps], dtype=torch.int32).to(dev),
-                              torch.tensor([sp[2] for sp in sps], dtype=torch.float32).to(dev),
-                              torch.tensor([sp[3] - (1 << 64) if sp[3] >= 1 << 63 else sp[3] for sp in sps], dtype=torch.long).to(dev),
-                              torch.full((len(sps),), int(d), dtype=torch.long).to(dev))
-        self._keep_first_logprobs(raw, tok)
-        return tok.tolist()
-
-    def _keep_first_logprobs(self, logits, tok):
-        """a logprob session: the first tokens' entries from the prefill's logits [R, V] and the tokens just chosen, both still on the device;
-        _admit copies row r into the tenant's entry 0.  No host read."""
-        if self.logprobs is not None:
-            self._first_lp = ops.token_logprobs(logits, tok.view(-1), self.logprobs)
-
     def _stops(self, stop_token_ids):
         s_ = sorted(int(i) for i in (stop_token_ids or ()))
         if len(s_) > self.stop_ids.shape[1]:
             raise ValueError("more stop ids than session(max_stop_ids=%d) holds" % self.stop_ids.shape[1])
         return s_
 
-    def _admit(self, t, first, L, max_new_tokens, stops, sp=GREEDY, row=0, con=None, ss=None):
-        """tenant t's state after its prefill: the first token is the prefill's (argmax, or _first_tokens' draw); row: its row of that prefill;
-        con: the request's automaton, advanced here once, on the host, with that first token; ss: _stop_sequences_arg's value, matched here
-        once, on the host, against that first token"""
+    def _request(self, stop_token_ids, temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                 constraint, stop_sequences, no_repeat_ngram_size, bad_words, min_new_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff):
+        """One request's arguments as a validated record, in one fixed order; nothing is touched.  stops: the sorted stop ids; sp / pp / bp / tp:
+        sampling_params', penalty_params', ban_params' and truncation_params' tuples; con: None or the TokenAutomaton, checked against the
+        session's sizes and the stop ids; ss: _stop_sequences_arg's value."""
+        stops = self._stops(stop_token_ids)
+        return _Request(stops, self._params(temperature, top_k, top_p, seed),
+                        self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias),
+                        self._check_constraint(self._constraint_arg(constraint), stops), self._stop_sequences_arg(stop_sequences),
+                        self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens),
+                        self._truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff))
+
+    def _first_tokens(self, logits, d, rows=slice(None)):
+        """the first token of each row of the prefill's logits [R, V] (they stay on the device) under its request's parameters, draw index d: the
+        cache row the token will occupy.  One host read, the one admission makes anyway.  rows: the tenants the R rows belong to, whose records
+        _admit has just written: every mask stage's rows form runs on the row the one before it left (penalised, constrained, banned,
+        truncated), the token is the argmax or serving_ops.sample_rows' draw under the tenants' own parameter arrays, and the
+        log-probabilities are still the raw rows'."""
+        raw = logits
+        for mask_rows, _ in self._masks:
+            logits = mask_rows(self, logits, rows)
         if self.sampling:
-            self._write_params(t, sp)
-        if self.logprobs is not None:                 # the turn's entries restart with it, as result() does
-            lp, top_id, top_lp = self._first_lp
-            self.lp[t, 0] = lp[row]
-            self.top_id[t, 0] = top_id[row]
-            self.top_lp[t, 0] = top_lp[row]
-            self.lp_n[t] = 1
-        reason = (1 if first in stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
-        if self.constraints:
-            self.c_n[t] = 1
-            if con is not None:
-                s_ = con.step(0, first)
-                self.c_state[t] = s_
-                reason |= 8 if con.is_final(s_) else 0
-        if self.stop_sequences:                       # the rule of the launch for n = 1: a one-token sequence equal to the first token is a hit
-            hit, hold = stop_sequence_scan([first], ss[0])
-            self._write_stop_sequences(t, ss, hit, hold, 1)
-            reason |= 16 if hit >= 0 else 0
-        self.stop_ids[t].fill_(-1)
-        if stops:
-            self.stop_ids[t, :len(stops)] = torch.tensor(stops, dtype=torch.long, device=self.dec.dev)
-        self.out[t].zero_()
-        self.out[t, 0] = first
-        self.tok[t, 0] = first
-        self.n[t] = 1
-        self.pos[t] = L
-        self.limit[t] = int(max_new_tokens)
-        self.done[t] = reason
-        self.active_flags[t] = reason == 0
+            if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
+                logits = logits.contiguous()
+            tok = ops.sample_rows(logits, self.temperature[rows], self.top_k[rows], self.top_p[rows], self.seed[rows],
+                                  torch.full((logits.shape[0],), int(d), dtype=torch.long).to(self.dec.dev))
+        else:
+            tok = torch.argmax(logits, dim=-1)
+        for after_rows, _ in self._after:
+            if after_rows is not None:
+                after_rows(self, raw, tok)
+        return tok.tolist()
+
+    def _admit(self, ts, reqs, logits, L, max_new_tokens, contexts, histories, fold=False):
+        """The one admission path, behind the prefill: tenants ts (consecutive slots; row r of the prefill's logits [R, V] is tenant ts[r]'s) with
+        their records reqs, at position L.  contexts[r]: the real tokens this admission adds to the tenant's context; histories[r]: ALL the
+        conversation's real tokens up to this turn (a ban session keeps them); fold: the next turn of a conversation (extend).  In order:
+        every record is written whole -- the stop ids and each feature's arrays, once; torch ops on the current stream, no host read --, the
+        first tokens are chosen from what was written (_first_tokens), and admission is finished per tenant: each feature's own part (the
+        constraint's host step and the stop-sequence scan on the first token, the log-probabilities' entry 0), the reason bits, and out / tok /
+        n / pos / limit / done / active."""
+        for t, req, context, history in zip(ts, reqs, contexts, histories):
+            self.stop_ids[t].fill_(-1)
+            if req.stops:
+                self.stop_ids[t, :len(req.stops)] = torch.tensor(req.stops, dtype=torch.long).to(self.dec.dev)
+            for write in self._writes:
+                write(self, t, req, context, history, fold)
+        first = self._first_tokens(logits, L, slice(ts[0], ts[-1] + 1))
+        for row, (t, req) in enumerate(zip(ts, reqs)):
+            tok = int(first[row])
+            reason = (1 if tok in req.stops else 0) | (2 if max_new_tokens <= 1 else 0) | (4 if L >= self.Lc else 0)
+            for admit in self._admits:
+                reason |= admit(self, t, req, tok, row)
+            self.out[t].zero_()
+            self.out[t, 0] = tok
+            self.tok[t, 0] = tok
+            self.n[t] = 1
+            self.pos[t] = L
+            self.limit[t] = int(max_new_tokens)
+            self.done[t] = reason
+            self.active_flags[t] = reason == 0
 
     @torch.no_grad()
     def submit(self, t, prompt, max_new_tokens=16, stop_token_ids=(), temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
@@ -2263,12 +2308,8 @@ class TenantSession:
         token is sampled from, behind every other mask and in front of top-k / top-p, and the first token obeys them too."""
         dec = self.dec
         assert 0 <= t < self.T and len(prompt) >= 1 and max_new_tokens >= 1
-        sp = self._params(temperature, top_k, top_p, seed)
-        pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
-        con = self._constraint_arg(constraint)
-        ss = self._stop_sequences_arg(stop_sequences)
-        bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
-        tp = self._truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        req = self._request(stop_token_ids, temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                            constraint, stop_sequences, no_repeat_ngram_size, bad_words, min_new_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff)
         self._check_tokens(prompt)
         self._check_conversation(prompt)
         if bool(self.active_flags[t]):
@@ -2278,18 +2319,12 @@ class TenantSession:
             raise ValueError("max_len too large, please reduce the input length")
         if L > self.Lc:
             raise ValueError("the padded prompt does not fit the KV cache")
-        stops = self._stops(stop_token_ids)
-        self._check_constraint(con, stops)
         ids = torch.zeros(1, L, dtype=torch.long)
         am = torch.zeros(1, L, dtype=torch.bool)
         ids[0, L - len(prompt):] = torch.tensor(prompt, dtype=torch.long)
         am[0, L - len(prompt):] = True
         logits = dec.tenant_view(t).prefill(ids.to(dec.dev), am.to(dec.dev), dec.cache_view(self.cache, t))      # clears valid[t], writes rows [0, L)
-        self._context(t, prompt, pp)
-        self._write_constraint(t, con, stops)
-        self._write_bans(t, bp, prompt, stops)
-        self._write_truncation(t, tp)
-        self._admit(t, int(self._first_tokens(logits, [sp], L, slice(t, t + 1))[0]), L, max_new_tokens, stops, sp, con=con, ss=ss)
+        self._admit([t], [req], logits, L, max_new_tokens, [prompt], [prompt])
         self._kv_start[t] = L - len(prompt)
 
     @torch.no_grad()
@@ -2323,13 +2358,8 @@ class TenantSession:
             raise IndexError("tenant %r: this session holds slots 0 .. %d" % (t, self.T - 1))
         assert max_new_tokens >= 1
         tokens = [int(i) for i in tokens]
-        stops = self._stops(stop_token_ids)
-        sp = self._params(temperature, top_k, top_p, seed)
-        pp = self._penalty_params(repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
-        con = self._check_constraint(self._constraint_arg(constraint), stops)
-        ss = self._stop_sequences_arg(stop_sequences)
-        bp = self._ban_params(no_repeat_ngram_size, bad_words, min_new_tokens)
-        tp = self._truncation_params(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        req = self._request(stop_token_ids, temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                            constraint, stop_sequences, no_repeat_ngram_size, bad_words, min_new_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff)
         self._check_tokens(tokens)
         active, pos, done, last = torch.stack([self.active_flags[t].long(), self.pos[t], self.done[t].long(), self.tok[t, 0]]).tolist()
         P, n = extend_plan(pos, self._kv_start[t], done, len(tokens), self.Lc, active=bool(active))
@@ -2340,11 +2370,7 @@ class TenantSession:
         ids = torch.tensor([[last] + tokens], dtype=torch.long).to(dec.dev)
         kvs = torch.tensor([self._kv_start[t]], dtype=torch.int32).to(dec.dev)
         logits = dec.tenant_view(t).prefill_chunk(ids, P, dec.cache_view(self.cache, t), kvs)      # marks valid[t, P : P + n], writes those rows
-        self._context(t, [last] + tokens, pp, fold=True)
-        self._write_constraint(t, con, stops)
-        self._write_bans(t, bp, conv, stops)
-        self._write_truncation(t, tp)
-        self._admit(t, int(self._first_tokens(logits, [sp], P + n, slice(t, t + 1))[0]), P + n, max_new_tokens, stops, sp, con=con, ss=ss)
+        self._admit([t], [req], logits, P + n, max_new_tokens, [[last] + tokens], [conv], fold=True)
 
     @torch.no_grad()
     def submit_all(self, prompts, max_new_tokens=16, stop_token_ids=None, temperature=0.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0,
@@ -2359,37 +2385,23 @@ class TenantSession:
         eta_cutoff: each one value for all or a list with one per tenant."""
         dec = self.dec
         assert max_new_tokens >= 1
-        bps = [self._ban_params(*a) for a in zip(self._per_tenant(no_repeat_ngram_size), self._per_tenant_bad_words(bad_words),
-                                                 self._per_tenant(min_new_tokens))]
-        tps = [self._truncation_params(*a) for a in zip(self._per_tenant(min_p), self._per_tenant(typical_p), self._per_tenant(epsilon_cutoff),
-                                                        self._per_tenant(eta_cutoff))]
-        sps = [self._params(*a) for a in zip(self._per_tenant(temperature), self._per_tenant(top_k), self._per_tenant(top_p),
-                                             self._per_tenant(seed))]
-        pps = [self._penalty_params(*a) for a in zip(self._per_tenant(repetition_penalty), self._per_tenant(presence_penalty),
-                                                     self._per_tenant(frequency_penalty), self._per_tenant(logit_bias))]
-        cons = [self._constraint_arg(c) for c in self._per_tenant(constraint)]
-        sss = [self._stop_sequences_arg(v) for v in self._per_tenant_stop_sequences(stop_sequences)]
+        per = [self._per_tenant(v) for v in (temperature, top_k, top_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+                                             constraint)]
+        per += [self._per_tenant_stop_sequences(stop_sequences), self._per_tenant(no_repeat_ngram_size), self._per_tenant_bad_words(bad_words)]
+        per += [self._per_tenant(v) for v in (min_new_tokens, min_p, typical_p, epsilon_cutoff, eta_cutoff)]
+        reqs = [self._request(stop_token_ids[t] if stop_token_ids else (), *(v[t] for v in per)) for t in range(self.T)]
         for p_ in prompts:
             self._check_tokens(p_)
             self._check_conversation(p_)
         if bool(self.active_flags.any()):
             raise RuntimeError("a tenant is still generating")
-        stops = [self._stops(stop_token_ids[t]) if stop_token_ids else [] for t in range(self.T)]
-        for t in range(self.T):
-            self._check_constraint(cons[t], stops[t])
         ids, am = dec.prepare(prompts)
         L = ids.shape[1]
         if L > self.Lc:
             raise ValueError("the padded prompts do not fit the KV cache")
         logits = dec.prefill(ids, am, self.cache)
+        self._admit(range(self.T), reqs, logits, L, max_new_tokens, prompts, prompts)
         for t in range(self.T):
-            self._context(t, prompts[t], pps[t])
-            self._write_constraint(t, cons[t], stops[t])
-            self._write_bans(t, bps[t], prompts[t], stops[t])
-            self._write_truncation(t, tps[t])
-        first = self._first_tokens(logits, sps, L)
-        for t in range(self.T):
-            self._admit(t, first[t], L, max_new_tokens, stops[t], sps[t], row=t, con=cons[t], ss=sss[t])
             self._kv_start[t] = L - len(prompts[t])
 
     # ------------------------------------------------------------ stepping
@@ -2399,58 +2411,29 @@ class TenantSession:
         logits = dec.forward(self.tok, None, self.cache, None, x=x, ragged=(self.pos, self.active_flags))
         if not (logits.stride(1) == 1 and logits.stride(0) % 8 == 0 and logits.data_ptr() % 16 == 0):
             raise RuntimeError("the lm_head output is not laid out for the step kernel (16-byte aligned rows)")
-        raw = logits                                  # (step_logprobs keeps reading the model's own row)
-        if self.penalties:                            # counts the token fed in, writes the row the step end chooses from
-            logits = ops.step_penalize(raw, self.plogits, self.hist, self.tok, self.active_flags, self.pen, self.bias_id, self.bias_val)
-        if self.constraints:                          # masks the (penalised) row by each tenant's automaton state; the state itself moves below
-            logits = ops.step_constrain(logits, self.clogits, self.c_state, self.c_off, self.c_tok, self.c_acc, self.stop_ids, self.active_flags)
-        if self.bans:                                 # masks what the tenant's own history forbids; wins over a positive bias and a constraint's edge
-            logits = ops.step_ban(logits, self.blogits, self.ctx, self.ctx_len, self.out, self.n, self.ban_ngram, self.ban_tok, self.ban_len,
-                                  self.ban_min, self.stop_ids, self.active_flags)
-        if self.truncation:                           # the last of the masks: cuts the tail of the row the others leave, at the tenant's temperature
-            logits = ops.step_truncate(logits, self.tlogits, self.temperature, self.trunc, self.active_flags)
+        raw = logits                                  # (the launches behind the step end keep reading the model's own row)
+        for _, mask_step in self._masks:
+            logits = mask_step(self, logits)
         if self.sampling:
             ops.step_end_sample(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc,
                                 self.temperature, self.top_k, self.top_p, self.seed)
         else:
             ops.step_end_ragged(logits, self.tok, self.out, self.n, self.pos, self.limit, self.stop_ids, self.active_flags, self.done, self.Lc)
-        if self.logprobs is not None:
-            ops.step_logprobs(raw, self.tok, self.n, self.lp_n, self.lp, self.top_id, self.top_lp)
-        if self.constraints:                          # follows the token just chosen; a tenant that reaches a final state retires here (reason 8)
-            ops.step_constrain_advance(self.tok, self.n, self.c_n, self.c_state, self.c_off, self.c_tok, self.c_next, self.c_acc,
-                                       self.active_flags, self.done)
-        if self.stop_sequences:                       # LAST: a turn that now ends with one of its sequences retires here (reason 16, OR-ed)
-            ops.step_stop_sequences(self.out, self.n, self.ss_n, self.ss_tok, self.ss_len, self.hit, self.hold, self.active_flags, self.done)
+        for _, after_step in self._after:
+            after_step(self, raw)
 
     def _state(self):
-        st = [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]]
-        if self.logprobs is not None:
-            st = st + [self.lp_n]
-        if self.penalties:                            # (the warm-up and the capture step would count their token twice otherwise)
-            st = st + [self.hist]
-        if self.constraints:                          # (... and would advance twice)
-            st = st + [self.c_state, self.c_n]
-        if self.stop_sequences:                       # (... and would leave a hit of the trial steps behind)
-            st = st + [self.ss_n, self.hit, self.hold]
-        return st
+        return [self.tok, self.pos, self.n, self.limit, self.active_flags, self.done, self.stop_ids, self.out, self.cache["valid"]] + self._trial
 
     def _runner(self):
         """The step as a captured hipGraph on the decoder's capture stream (TenantDecoder._graph_runner's discipline: a warm-up step on that
         stream, the capture, then every state tensor put back).  All request state is device data, so the graph is keyed by the glue switches
-        and the kind of session (greedy or sampling: another last launch; its logprobs count: one more launch on its own buffers; penalties:
-        one more launch in front of the last; constraints: one more in front of the last and one behind it; stop sequences: one more at the very end, on a table of the
-        session's two sizes; bans: one more in front of the step end, on a table of the session's two sizes; truncation: one more in front of the
-        step end) alone."""
+        and the kind of session alone: greedy or sampling, the logprobs count, penalties, constraints, and what the later stages' set-up blocks
+        added to the key (a session without them keeps the key it had), then the decoder's KV-cache mode."""
         dec = self.dec
         key = (dec.fuse_glue, dec.fuse_qkv_norm, dec.fuse_gateup_norm, dec.norm_handoff, FusedDeltaLinear.use_tiled, self.out.data_ptr(),
-               self.sampling, self.logprobs, self.penalties, self.constraints)
-        if self.stop_sequences:                       # (a session without them keeps the key it had)
-            key = key + (True, self.ss_tok.shape[1], self.ss_tok.shape[2])
-        if self.bans:                                 # (likewise; the launch keeps no counter, so _state() gains nothing)
-            key = key + ("bans", self.ban_tok.shape[1], self.ban_tok.shape[2])
-        if self.truncation:                           # (likewise)
-            key = key + ("truncation",)
-        if dec.kv_cache is not None:                  # (likewise: another attention launch; its scales are device data)
+               self.sampling, self.logprobs, self.penalties, self.constraints) + self._key
+        if dec.kv_cache is not None:                  # (another attention launch; its scales are device data)
             key = key + (dec.kv_cache,)
         g = self._graphs.get(key)
         if g is None:

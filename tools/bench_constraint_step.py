@@ -14,13 +14,14 @@ state whose slice is the session's whole edge array).  Then the device time of t
 with N(0, 3^2) logits: step_constrain in the three situations, constrain_rows, step_constrain_advance (behind a one-element add that moves the
 counter, and that add alone), step_penalize / step_end_sample re-measured next to them, and step_end_sample on rows the mask has
 left 1 / 64 / 4096 finite elements in: the sampling launch's own time depends on the row it is given."""
-import argparse
 import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
+
+import step_ab  # noqa: E402
 
 SAMPLE = dict(temperature=1.0, top_k=50, top_p=0.9)
 
@@ -41,23 +42,12 @@ def ring_of_choices(TokenAutomaton, vocab, g, choices=64, length=4):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="mistral-7b")
-    ap.add_argument("--tenants", type=int, default=6)
-    ap.add_argument("--kv-len", type=int, default=512)
-    ap.add_argument("--layers", type=int, default=None)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--warm-steps", type=int, default=200, help="replays of every arm before the first timed round (clocks)")
-    ap.add_argument("--kernel-iters", type=int, default=200)
-    args = ap.parse_args()
-    from bitdelta_amd import dist as bdd
+    args = step_ab.parse_args()
     from bitdelta_amd import serving_ops as ops
     from bitdelta_amd.constraint import TokenAutomaton
     from bitdelta_amd.serving_loop import TenantDecoder, penalty_row
     dev = torch.device("cuda", 0)
     T = args.tenants
-    assert max(args.warm_steps, args.steps + 1) < 256, "the arms must not run into the end of the cache (kv-len + 256 rows)"
     dec = TenantDecoder.synthetic(args.model, T, dev, dtype=torch.float16, seed=4321, layers=args.layers, max_len=args.kv_len + 256)
     vocab = dec.cfg[5]
     g = torch.Generator().manual_seed(4321)
@@ -65,40 +55,21 @@ def main():
     trie = [ring_of_choices(TokenAutomaton, vocab, g) for _ in range(T)]
     aset = [TokenAutomaton.allowed_set(torch.randperm(vocab, generator=g)[:4096].tolist()) for _ in range(T)]
 
-    arms = {}
+    arms, sessions = {}, []
 
     def arm(name, constraints, cons):
         sess = dec.session(sampling=True, constraints=constraints)
         sess.submit_all(prompts, max_new_tokens=1 << 30, seed=list(range(1, T + 1)), **SAMPLE, **({"constraint": cons} if constraints else {}))
         assert all(sess.active())
-        snap = [v.clone() for v in sess._state()]
-
-        def restore():
-            for v, s_ in zip(sess._state(), snap):
-                v.copy_(s_)
-        run = sess._runner()
-        restore()
-        arms[name] = (run, restore, sess)
+        arms[name] = step_ab.capture(sess)
+        sessions.append(sess)
     arm("sample", False, None)
     arms["sample_b"] = arms["sample"]
     arm("con_none", True, None)
     arm("con_trie", True, trie)
     arm("con_set", True, aset)
     arms = {n: arms[n] for n in ("sample", "con_none", "con_trie", "con_set", "sample_b")}
-    for run, restore, _ in arms.values():
-        restore()
-        for _ in range(args.warm_steps):
-            run()
-    torch.cuda.synchronize()
-    assert all(all(s.active()) for _, _, s in arms.values()), "a tenant retired during the warm-up: the arm would time an idle step"
-    ms = {n: [] for n in arms}
-    for _ in range(args.rounds):
-        for n, (run, restore, _) in arms.items():
-            restore()
-            run()
-            ms[n].append(bdd.timed_region(run, args.steps, device_sync=torch.cuda.synchronize) / args.steps * 1e3)
-    assert all(all(s.active()) for _, _, s in arms.values())
-    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    ms, med = step_ab.time_arms(arms, args, sessions)
     base = (med["sample"] + med["sample_b"]) / 2
 
     # the launches alone: device time per launch on the step's shape, the automata at the session's default sizes
@@ -141,30 +112,7 @@ def main():
         a_n.add_(1)
         ops.step_constrain_advance(a_tok, a_n, a_cn, a_state, p_set[0], p_set[1], p_set[2], p_set[3], a_act, a_done)
 
-    side = torch.cuda.Stream(device=dev)
-
-    def kernel_us(fn):
-        """--kernel-iters launches in a row inside ONE captured graph (no host in the loop): replay time / launches, median of 5 replays"""
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr, stream=side):
-            for _ in range(args.kernel_iters):
-                fn()
-        gr.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        times = []
-        for _ in range(5):
-            e0.record()
-            gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1) / args.kernel_iters * 1e3)
-        return sorted(times)[len(times) // 2]
+    kernel_us = step_ab.kernel_timer(dev, args.kernel_iters)
     kern = {
         "step_constrain/none": kernel_us(lambda: ops.step_constrain(logits, clogits, free, p_trie[0], p_trie[1], p_trie[3], stops, act)),
         "step_constrain/trie_root_64_edges": kernel_us(lambda: ops.step_constrain(logits, clogits, root, p_trie[0], p_trie[1], p_trie[3], stops, act)),
@@ -188,14 +136,13 @@ def main():
                                         tau, k, pp, seed))
     moved = T * vocab * 4
     out = {"model": args.model, "tenants": T, "kv_len": args.kv_len, "layers": len(dec.layers), "vocab": vocab, "steps": args.steps,
-           "rounds": args.rounds, "arms": {n: {"min_ms": min(v), "median_ms": med[n], "all_ms": [round(x, 4) for x in v]} for n, v in ms.items()},
+           "rounds": args.rounds, "arms": step_ab.arms_json(ms, med),
            "aa_spread_sample_pct": abs(med["sample_b"] / med["sample"] - 1) * 100,
            "over_sample_pct": {n: (med[n] / base - 1) * 100 for n in arms if n.startswith("con")},
            "over_sample_us": {n: (med[n] - base) * 1e3 for n in arms if n.startswith("con")},
            "launch_us_in_graph": {n: round(v, 3) for n, v in kern.items()}, "mask_launch_bytes": moved}
     print(json.dumps(out))
-    for n, a in out["arms"].items():
-        print(f"# {n:16s} min {a['min_ms']:.4f}  median {a['median_ms']:.4f} ms/step", file=sys.stderr)
+    step_ab.print_arms(out["arms"], 16)
     print(f"# A/A spread (sample): {out['aa_spread_sample_pct']:.2f} %;  over the sampling session's step: " +
           ", ".join(f"{n} {v:+.2f} % ({out['over_sample_us'][n]:+.1f} us)" for n, v in out["over_sample_pct"].items()), file=sys.stderr)
     for n, v in out["launch_us_in_graph"].items():

@@ -10,7 +10,6 @@ own KV cache.  A prompt of 64 tokens is submitted, then every tenant's position 
 values (prompts stop at 1024 tokens; the step's time depends on the rows it reads, not on what they hold), so the arms' tokens are not compared
 here -- tests/test_gpu_kv8_*.py hold the arithmetic.  Then the device time of the attention launch alone on the step's shape, both forms, with
 the K / V bytes it has to read per launch and the resulting bytes/s, and the resident cache bytes of both decoders."""
-import argparse
 import json
 import os
 import sys
@@ -18,24 +17,15 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+import step_ab  # noqa: E402
+
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="mistral-7b")
-    ap.add_argument("--tenants", type=int, default=6)
-    ap.add_argument("--kv-len", type=int, default=512)
-    ap.add_argument("--layers", type=int, default=None)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--warm-steps", type=int, default=100, help="replays of every arm before the first timed round (clocks)")
-    ap.add_argument("--kernel-iters", type=int, default=100)
-    args = ap.parse_args()
-    from bitdelta_amd import dist as bdd
+    args = step_ab.parse_args(warm_steps=100, kernel_iters=100)
     from bitdelta_amd import serving_ops as ops
     from bitdelta_amd.serving_loop import TenantDecoder
     dev = torch.device("cuda", 0)
     T = args.tenants
-    assert max(args.warm_steps, args.steps + 1) < 256, "the arms must not run into the end of the cache (kv-len + 256 rows)"
     max_len = args.kv_len + 256
     dec = TenantDecoder.synthetic(args.model, T, dev, dtype=torch.float16, seed=4321, layers=args.layers, max_len=max_len)
     twin = TenantDecoder(dec.cfg, T, dev, torch.float16, max_len=max_len, kv_cache="fp8")
@@ -56,29 +46,12 @@ def main():
         sess.cache["valid"][:, :args.kv_len] = True
         sess.pos.fill_(args.kv_len)
         resident[name] = sum(c.numel() * c.element_size() for c in sess.cache["k"] + sess.cache["v"])
-        snap = [v.clone() for v in sess._state()]
-
-        def restore():
-            for v, s_ in zip(sess._state(), snap):
-                v.copy_(s_)
-        run = sess._runner()
-        restore()
-        arms[name] = (run, restore)
+        arms[name] = step_ab.capture(sess)
     arm("fp16", dec)
     arms["fp16_b"] = arms["fp16"]
     arm("fp8", twin)
     arms = {n: arms[n] for n in ("fp16", "fp8", "fp16_b")}
-    for run, restore in arms.values():
-        restore()
-        for _ in range(args.warm_steps):
-            run()
-    ms = {n: [] for n in arms}
-    for _ in range(args.rounds):
-        for n, (run, restore) in arms.items():
-            restore()
-            run()
-            ms[n].append(bdd.timed_region(run, args.steps, device_sync=torch.cuda.synchronize) / args.steps * 1e3)
-    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    ms, med = step_ab.time_arms(arms, args)
     base = (med["fp16"] + med["fp16_b"]) / 2
 
     # the launch alone: device time per decode attention launch on the step's shape (ragged form, every tenant near kv-len)
@@ -90,30 +63,7 @@ def main():
     pos = torch.tensor([args.kv_len + 3 * t for t in range(T)], dtype=torch.long, device=dev)
     valid = (torch.arange(Lc, device=dev)[None, :] < pos[:, None]).contiguous()
     act = torch.ones(T, dtype=torch.bool, device=dev)
-    side = torch.cuda.Stream(device=dev)
-
-    def kernel_us(fn):
-        """--kernel-iters launches in a row inside ONE captured graph (no host in the loop): replay time / launches, median of 5 replays"""
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr, stream=side):
-            for _ in range(args.kernel_iters):
-                fn()
-        gr.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        times = []
-        for _ in range(5):
-            e0.record()
-            gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1) / args.kernel_iters * 1e3)
-        return sorted(times)[len(times) // 2]
+    kernel_us = step_ab.kernel_timer(dev, args.kernel_iters)
     kern = {}
     for rep in ("", "_b"):                                  # each twice, alternated: the pair's own spread
         kern["fp16" + rep] = kernel_us(lambda: ops.decode_attention_ragged(qkv, dec.cos, dec.sin, kc, vc, valid, pos, act, heads, kvh))
@@ -122,12 +72,11 @@ def main():
     launch = {n: {"us": round(v, 3), "kv_bytes": rows * (1 if n.startswith("fp8") else 2),
                   "GBps": round(rows * (1 if n.startswith("fp8") else 2) / v / 1e3, 1)} for n, v in kern.items()}
     out = {"model": args.model, "tenants": T, "kv_len": args.kv_len, "layers": len(dec.layers), "max_len": max_len, "steps": args.steps,
-           "rounds": args.rounds, "arms": {n: {"min_ms": min(v), "median_ms": med[n], "all_ms": [round(x, 4) for x in v]} for n, v in ms.items()},
+           "rounds": args.rounds, "arms": step_ab.arms_json(ms, med),
            "aa_spread_fp16_pct": abs(med["fp16_b"] / med["fp16"] - 1) * 100, "fp8_over_fp16_pct": (med["fp8"] / base - 1) * 100,
            "fp8_over_fp16_us": (med["fp8"] - base) * 1e3, "launch_in_graph": launch, "resident_cache_bytes": resident}
     print(json.dumps(out))
-    for n, a in out["arms"].items():
-        print(f"# {n:8s} min {a['min_ms']:.4f}  median {a['median_ms']:.4f} ms/step", file=sys.stderr)
+    step_ab.print_arms(out["arms"], 8)
     print(f"# A/A spread (fp16): {out['aa_spread_fp16_pct']:.2f} %;  fp8 cache over the 16-bit cache's step: {out['fp8_over_fp16_pct']:+.2f} % "
           f"({out['fp8_over_fp16_us']:+.1f} us)", file=sys.stderr)
     for n, v in launch.items():

@@ -13,7 +13,6 @@ tenant with 16 random sequences of 32 tokens).  Random sequences over the whole 
 and 16 x 32, empty, random (a pair is decided by its first comparison) and the worst case -- a row of one repeated token under sequences of
 that token with another last id, so that every (sequence, length) pair compares its whole length and nothing ever hits -- and with a counter
 that did not move; step_end_sample re-measured next to them."""
-import argparse
 import json
 import os
 import sys
@@ -21,66 +20,38 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+import step_ab  # noqa: E402
+
 SAMPLE = dict(temperature=1.0, top_k=50, top_p=0.9)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="mistral-7b")
-    ap.add_argument("--tenants", type=int, default=6)
-    ap.add_argument("--kv-len", type=int, default=512)
-    ap.add_argument("--layers", type=int, default=None)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--warm-steps", type=int, default=200, help="replays of every arm before the first timed round (clocks)")
-    ap.add_argument("--kernel-iters", type=int, default=200)
-    args = ap.parse_args()
-    from bitdelta_amd import dist as bdd
+    args = step_ab.parse_args()
     from bitdelta_amd import serving_ops as ops
     from bitdelta_amd.serving_loop import TenantDecoder
     dev = torch.device("cuda", 0)
     T = args.tenants
-    assert max(args.warm_steps, args.steps + 1) < 256, "the arms must not run into the end of the cache (kv-len + 256 rows)"
     dec = TenantDecoder.synthetic(args.model, T, dev, dtype=torch.float16, seed=4321, layers=args.layers, max_len=args.kv_len + 256)
     vocab = dec.cfg[5]
     g = torch.Generator().manual_seed(4321)
     prompts = [torch.randint(1, vocab, (args.kv_len,), generator=g).tolist() for _ in range(T)]
     rand_seqs = lambda q, w: [[torch.randint(1, vocab, (w,), generator=g).tolist() for _ in range(q)] for _ in range(T)]
 
-    arms = {}
+    arms, sessions = {}, []
 
     def arm(name, kw, seqs):
         sess = dec.session(sampling=True, **kw)
         sess.submit_all(prompts, max_new_tokens=1 << 30, seed=list(range(1, T + 1)), **SAMPLE, **({"stop_sequences": seqs} if seqs else {}))
         assert all(sess.active())
-        snap = [v.clone() for v in sess._state()]
-
-        def restore():
-            for v, s_ in zip(sess._state(), snap):
-                v.copy_(s_)
-        run = sess._runner()
-        restore()
-        arms[name] = (run, restore, sess)
+        arms[name] = step_ab.capture(sess)
+        sessions.append(sess)
     arm("sample", {}, None)
     arms["sample_b"] = arms["sample"]
     arm("ss_none", dict(stop_sequences=True), None)
     arm("ss_4x8", dict(stop_sequences=True), rand_seqs(4, 8))
     arm("ss_16x32", dict(stop_sequences=True, max_stop_sequences=16, max_stop_sequence_len=32), rand_seqs(16, 32))
     arms = {n: arms[n] for n in ("sample", "ss_none", "ss_4x8", "ss_16x32", "sample_b")}
-    for run, restore, _ in arms.values():
-        restore()
-        for _ in range(args.warm_steps):
-            run()
-    torch.cuda.synchronize()
-    assert all(all(s.active()) for _, _, s in arms.values()), "a tenant retired during the warm-up: the arm would time an idle step"
-    ms = {n: [] for n in arms}
-    for _ in range(args.rounds):
-        for n, (run, restore, _) in arms.items():
-            restore()
-            run()
-            ms[n].append(bdd.timed_region(run, args.steps, device_sync=torch.cuda.synchronize) / args.steps * 1e3)
-    assert all(all(s.active()) for _, _, s in arms.values())
-    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    ms, med = step_ab.time_arms(arms, args, sessions)
     base = (med["sample"] + med["sample_b"]) / 2
 
     # the launch alone: device time per launch, the counter moved by a one-element add in front of it so that every launch does its work
@@ -112,30 +83,7 @@ def main():
             ops.step_stop_sequences(o, s["n"], s["ss_n"], s["tok"], s["lens"], s["hit"], s["hold"], s["act"], s["done"])
         return fn
 
-    side = torch.cuda.Stream(device=dev)
-
-    def kernel_us(fn):
-        """--kernel-iters launches in a row inside ONE captured graph (no host in the loop): replay time / launches, median of 5 replays"""
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr, stream=side):
-            for _ in range(args.kernel_iters):
-                fn()
-        gr.replay()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        times = []
-        for _ in range(5):
-            e0.record()
-            gr.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1) / args.kernel_iters * 1e3)
-        return sorted(times)[len(times) // 2]
+    kernel_us = step_ab.kernel_timer(dev, args.kernel_iters)
     kern = {"add_1+step_stop_sequences/" + n: kernel_us(launch(o, s)) for n, (o, s) in cases.items()}
     for n, (o, s) in cases.items():
         assert int(s["n"].max()) <= cap and s["ss_n"].tolist() == s["n"].tolist() and all(s["act"].tolist()) and s["hit"].tolist() == [-1] * T, n
@@ -157,14 +105,13 @@ def main():
     kern["step_end_sample/k50_p90"] = kernel_us(lambda: ops.step_end_sample(logits, st["tok"], st["out"], st["n"], st["pos"], st["limit"], st["stop"],
                                                                             st["act"], st["done"], 1 << 30, tau, k, pp, seed))
     res = {"model": args.model, "tenants": T, "kv_len": args.kv_len, "layers": len(dec.layers), "vocab": vocab, "steps": args.steps,
-           "rounds": args.rounds, "arms": {n: {"min_ms": min(v), "median_ms": med[n], "all_ms": [round(x, 4) for x in v]} for n, v in ms.items()},
+           "rounds": args.rounds, "arms": step_ab.arms_json(ms, med),
            "aa_spread_sample_pct": abs(med["sample_b"] / med["sample"] - 1) * 100,
            "over_sample_pct": {n: (med[n] / base - 1) * 100 for n in arms if n.startswith("ss")},
            "over_sample_us": {n: (med[n] - base) * 1e3 for n in arms if n.startswith("ss")},
            "launch_us_in_graph": {n: round(v, 3) for n, v in kern.items()}}
     print(json.dumps(res))
-    for n, a in res["arms"].items():
-        print(f"# {n:16s} min {a['min_ms']:.4f}  median {a['median_ms']:.4f} ms/step", file=sys.stderr)
+    step_ab.print_arms(res["arms"], 16)
     print(f"# A/A spread (sample): {res['aa_spread_sample_pct']:.2f} %;  over the sampling session's step: " +
           ", ".join(f"{n} {v:+.2f} % ({res['over_sample_us'][n]:+.1f} us)" for n, v in res["over_sample_pct"].items()), file=sys.stderr)
     for n, v in res["launch_us_in_graph"].items():
