@@ -113,7 +113,7 @@ def delta_bmm(a, b, *, out=None, out_dtype=None, round_mode=1, alpha=None, accum
     return out
 
 
-def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=None, out=None):
+def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=None, out=None, weight_scale=None):
     """Fused 16-bit base + 1-bit delta Linear:  y[i] = x[i] . weight^T + alpha[i] * (x[i] . S[i])  in ONE launch.
 
     x: (B, M, K); weight: (N, K) rows k-contiguous; mask: (B or 1, K/32, N) int32; alpha: fp32 (B or 1, groups).
@@ -124,7 +124,13 @@ def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=
     path of the fused GEMM at M > 16 (output rounded, then the sum: the two roundings of the separate ops); a separate add otherwise.
     out: optional (B, M, N) destination of out_dtype with unit column stride (e.g. a peer-mapped all-reduce buffer: the row-parallel
     Linear of tp.py writes its fp32 partial sums straight into it); not combined with `residual`.
+    INT8 base weight (bd_binary_linear_w8; M >= 2, N % 16 == 0, K % 128 == 0): weight = quant.tile_weight_int8(CB) (int8, shape [N, K] -- the
+    decode copy, the one resident form of an int8 base) and weight_scale = quant.weight_scale(SCB) (fp32 [N]):
+    y = weight_scale * (x . CB^T) + alpha * (x . S), the scale on the finished fp32 base sum; `residual` is added before the one rounding.
+    ValueError for an int8 weight without a scale (or a scale with a 16-bit weight), M == 1 and shapes outside the envelope.
     """
+    if weight.dtype == torch.int8 or weight_scale is not None:
+        return _binary_linear_w8(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_scale)
     require_gpu(x, weight, mask, alpha, residual, out)
     assert x.dim() == 3 and mask.dim() == 3 and weight.dim() == 2
     B, M, K = x.shape
@@ -162,6 +168,51 @@ def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=
     if residual is not None and not fused_residual:
         residual += y
         return residual
+    return y
+
+
+def _binary_linear_w8(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_scale):
+    """binary_linear's int8 form: one launch of bd_binary_linear_w8 over the tile-major bytes.  The refusals come first (they need no device)."""
+    assert x.dim() == 3 and mask.dim() == 3 and weight.dim() == 2
+    if weight.dtype != torch.int8:
+        raise ValueError("weight_scale goes with the int8 tile-major weight (quant.tile_weight_int8), not with a %s weight" % weight.dtype)
+    if weight_scale is None:
+        raise ValueError("an int8 weight needs weight_scale = quant.weight_scale(SCB), fp32 [N]")
+    B, M, K = x.shape
+    N = weight.shape[0]
+    if M == 1:
+        raise ValueError("one row per batch entry is a decode launch: binary_linear_decode(..., weight_scale=...)")
+    if N % 16 or K % 128 or K == 0 or N == 0 or weight.shape[1] != K or not weight.is_contiguous():
+        raise ValueError("int8 base: a contiguous [N, K] tile-major weight with N % 16 == 0 and K % 128 == 0 is required")
+    if weight_scale.dtype != torch.float32 or tuple(weight_scale.shape) != (N,) or not weight_scale.is_contiguous():
+        raise ValueError("weight_scale: contiguous fp32 [N]")
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.stride(2) != 1 or x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(1) % 8:
+        raise ValueError("int8 base: fp16 / bf16 activations with 16-byte aligned, k-contiguous rows are required")
+    if weight.data_ptr() % 16 or weight_scale.data_ptr() % 16 or N % groups:
+        raise ValueError("int8 base: 16-byte aligned weight and weight_scale, groups dividing N")
+    require_gpu(x, weight, mask, alpha, residual, out, weight_scale)
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and mask.shape[1] * 32 == K and mask.shape[2] == N and mask.shape[0] in (1, B)
+    out_dtype = out_dtype or x.dtype
+    alpha = alpha.detach()
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    alpha = alpha.reshape(-1, groups)
+    assert alpha.shape[0] in (1, B)
+    sPb = 0 if (mask.shape[0] == 1 and B > 1) else mask.stride(0)
+    sAlb = 0 if alpha.shape[0] == 1 else groups
+    if residual is not None:
+        assert out is None, "out= and residual= are exclusive"
+        assert residual.shape == (B, M, N) and residual.dtype == out_dtype and residual.stride(2) == 1
+        y = residual
+    elif out is not None:
+        assert out.shape == (B, M, N) and out.dtype == out_dtype and out.stride(2) == 1 and out.device == x.device
+        y = out
+    else:
+        y = torch.empty((B, M, N), device=x.device, dtype=out_dtype)
+    with torch.cuda.device(x.device):
+        check(lib().bd_binary_linear_w8(ptr(x), ptr(weight), ptr(weight_scale), ptr(mask), ptr(alpha), ptr(y), B, M, N, K, x.stride(0), x.stride(1),
+                                        sPb, sAlb, groups, y.stride(0), y.stride(1), DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype],
+                                        1 if residual is not None else 0, stream_ptr()), "binary_linear_w8")
     return y
 
 

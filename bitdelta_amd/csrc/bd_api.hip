@@ -15,6 +15,7 @@
 #include "bd_gemm_pf.h"
 #include "bd_gemm_fx.h"
 #include "bd_gemm_w4.h"
+#include "bd_gemm_w8.h"
 #include "bd_gemv.h"
 #include "bd_gemv_stream.h"
 #include "bd_gemv_rows.h"
@@ -1471,6 +1472,30 @@ static int dispatch_quant(const Problem& q) {
     return launch_gemv_stream_chunk(q);
 }
 
+// ---- bd_binary_linear_w8: the int8 base at M >= 2 (gemm_w8_kernel, bd_gemm_w8.h).  The whole dispatch rule: a workgroup covers 16 rb rows x
+// 16 nw columns (one 16-column tile per wave), and only M picks the tile -- few rows take the 4-wave, 64-column group, so that an extend of a few
+// tokens or a 6 x 64 request prefill spreads over N / 64 x B workgroups instead of N / 128; above 64 rows the 8-wave 128 x 128 tile feeds 8
+// MFMAs from each widened fragment and shares one X stage among 8 column tiles.
+struct W8Plan { int rb, nw, tiles_m, groups; };
+inline W8Plan w8_plan(int M, int N) {
+    W8Plan pl;
+    pl.rb = M <= 16 ? 1 : M <= 32 ? 2 : M <= 64 ? 4 : 8;
+    pl.nw = pl.rb == 8 ? 8 : 4;
+    pl.tiles_m = (M + 16 * pl.rb - 1) / (16 * pl.rb);
+    pl.groups = (N + 16 * pl.nw - 1) / (16 * pl.nw);
+    return pl;
+}
+template <int DT> static int launch_gemm_w8(const W8Params& p, const W8Plan& pl, int B, hipStream_t st) {
+    const dim3 grid((unsigned)(pl.tiles_m * pl.groups), (unsigned)B), block(64 * pl.nw);
+    switch (pl.rb) {
+        case 1: hipLaunchKernelGGL((gemm_w8_kernel<DT, 1, 4>), grid, block, 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_w8_kernel<DT, 2, 4>), grid, block, 0, st, p); break;
+        case 4: hipLaunchKernelGGL((gemm_w8_kernel<DT, 4, 4>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((gemm_w8_kernel<DT, 8, 8>), grid, block, 0, st, p); break;
+    }
+    return launch_status();
+}
+
 // `q` arrives with what the entry point fuses around the Linear or says about its base weight, filled by name: norm_w / sNw / eps / epilogue,
 // ssq_in / ssq_out / xw_out, pn_*, and wscale (int8: its presence is the signal) or q4p / q4_group (4-bit); everything else is set here.
 static int binary_linear_impl(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B, int M,
@@ -1636,6 +1661,28 @@ extern "C" int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, cons
     e.q4p = qparams; e.q4_group = group_size;
     return binary_linear_impl(X, W4, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
                               accumulate, 2, t_pad, nullptr, 0, stream, e);
+}
+
+extern "C" int bd_binary_linear_w8(const void* X, const int8_t* W8, const float* wscale, const int32_t* P, const float* alpha, void* Y,
+                                   int B, int M, int N, int K, int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                                   int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, void* stream) {
+    if (B < 0 || M < 0 || N < 0 || K < 0) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (out_dtype != dtype && out_dtype != BD_F32) return BD_E_BAD_DTYPE;
+    if (B == 0 || M == 0) return BD_OK;
+    if (!X || !W8 || !wscale || !P || !alpha || !Y) return BD_E_NULL;
+    if (M < 2 || N < 16 || N % 16 || K < 128 || K % 128 || B > 65535) return BD_E_BAD_SHAPE;      // (M == 1: bd_binary_linear_decode_w8)
+    if (G < 1 || N % G) return BD_E_BAD_GROUPS;
+    if (!aligned16(X) || sXb % 8 || sXm % 8 || !aligned16(W8) || !aligned16(wscale) || sPb < 0 || sAlb < 0) return BD_E_BAD_SHAPE;
+    const W8Plan pl = w8_plan(M, N);
+    if ((int64_t)pl.tiles_m * pl.groups > 0x7fffffffll) return BD_E_BAD_SHAPE;
+    W8Params p{};
+    p.X = (const unsigned short*)X; p.W8 = W8; p.wscale = wscale; p.P = (const uint32_t*)P; p.alpha = alpha; p.C = Y;
+    p.M = M; p.N = N; p.K = K; p.gsz = N / G; p.tiles_m = pl.tiles_m;
+    p.sXb = sXb; p.sXm = sXm; p.sPb = sPb; p.sAlb = sAlb; p.sCb = sYb; p.sCm = sYm;
+    p.out_f32 = out_dtype == BD_F32; p.accumulate = accumulate ? 1 : 0;
+    p.vec = ((uintptr_t)Y % (p.out_f32 ? 16 : 8) == 0) && sYb % 4 == 0 && sYm % 4 == 0;
+    return dtype == BD_BF16 ? launch_gemm_w8<DT_BF16>(p, pl, B, (hipStream_t)stream) : launch_gemm_w8<DT_F16>(p, pl, B, (hipStream_t)stream);
 }
 
 extern "C" int bd_binary_linear_residual(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B,

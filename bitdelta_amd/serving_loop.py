@@ -125,7 +125,7 @@ class FusedDeltaLinear(nn.Module):
     tile_decode_weight = True     # keep a tile-major decode copy of the base weight (class switch)
 
     def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True, base_int8=False, base_gptq4=False, group_size=128,
-                 gptq4=None, dtype=None):
+                 gptq4=None, dtype=None, dense_base=True):
         """decode_copies=False skips the decode-only copies (packed sign words, tile-major base weight): a prefill-only user.
         base_int8=True: the (concatenated, interleaved) base is quantised once to the LLM.int8 vector-wise format (quant.quantize_base_int8); the
         16-bit `weight` becomes the reference-dequantised weight (what bitdelta/misc.py dequantize_model leaves in the model: prefill and every
@@ -134,8 +134,14 @@ class FusedDeltaLinear(nn.Module):
         the base is quantised once (quant.quantize_base_gptq4), `weight` becomes quant.dequantize_base_gptq4 of it, and the decode copy is the
         tile-major nibbles + one packed (scale, zero) dword per (group, column).  gptq4 = one (qweight, qzeros, scales) triple per projection (a
         GPTQ checkpoint) takes the place of the quantiser AND of `weights`, which must then be None: the widths come from the triples, the
-        group size from the checkpoint (K / scales.shape[0]) and `dtype` says what the dequantised weight is cast to.  from_gptq4 spells it."""
+        group size from the checkpoint (K / scales.shape[0]) and `dtype` says what the dequantised weight is cast to.  from_gptq4 spells it.
+        dense_base=False (with base_int8): the 16-bit `weight` is NOT kept (`self.weight is None`) -- the int8 tile-major bytes are the one
+        resident copy of the base, and every launch with more than one row per tenant runs bd_binary_linear_w8 on them (prefill, extend,
+        chunks, scoring); the fused SwiGLU / residual + norm prefill forms are not offered, the layer takes its separate launches."""
         super().__init__()
+        if not dense_base and not base_int8:
+            raise ValueError("dense_base=False drops the 16-bit base weight: it needs base_int8=True (the int8 bytes are then the only copy)")
+        self.dense_base = bool(dense_base)
         self.base_int8 = bool(base_int8)
         self.base_gptq4 = bool(base_gptq4)
         self.group_size = int(group_size)
@@ -163,7 +169,7 @@ class FusedDeltaLinear(nn.Module):
         cb = None
         if self.base_int8:
             cb, scb = quantize_base_int8(weight)
-            weight = dequantize_base_int8(cb, scb, weight.dtype)
+            weight = dequantize_base_int8(cb, scb, weight.dtype) if self.dense_base else None      # (never built when it is not kept)
             self.register_buffer("wscale", weight_scale(scb))
         else:
             self.wscale = None
@@ -175,7 +181,8 @@ class FusedDeltaLinear(nn.Module):
             self.register_buffer("group_params", pack_gptq4_params(qz, sc) if weight.shape[0] % 16 == 0 else None)
         else:
             self.group_params = None
-        self.register_buffer("weight", weight.contiguous())
+        self.N, self.K = mask.shape[2], mask.shape[1] * 32
+        self.register_buffer("weight", weight.contiguous() if self.dense_base else None)
         self.register_buffer("mask", mask.contiguous())
         self.register_buffer("alpha", alpha.contiguous())                                        # [T, G]
         self.groups = alpha.shape[1]
@@ -183,7 +190,7 @@ class FusedDeltaLinear(nn.Module):
         # the reference layout
         self.register_buffer("mask_packed", pack_decode_masks(self.mask) if (decode_copies and self.mask.shape[0] <= 16) else None)
         # ... and of the base weight in the kernel's tile-major order (one contiguous 4-KiB block per stage; +2 bytes per weight of HBM)
-        N, K = self.weight.shape
+        N, K = self.N, self.K
         tiled = self.mask_packed is not None and self.tile_decode_weight and N % 16 == 0 and K % 128 == 0
         if self.base_int8:        # the decode copy IS the int8 weight: without it the mode would silently stream 16 bits
             assert tiled, "base_int8 needs the decode copies: N % 16 == 0, K % 128 == 0, at most 16 tenants"
@@ -203,7 +210,7 @@ class FusedDeltaLinear(nn.Module):
     def _decode_ok(self, x):
         B, M, K = x.shape
         return self.mask_packed is not None and B == self.mask.shape[0] and B * M <= 16 and \
-            decode_shape_ok(B, M, self.weight.shape[0], K, B) and x.data_ptr() % 16 == 0 and \
+            decode_shape_ok(B, M, self.N, K, B) and x.data_ptr() % 16 == 0 and \
             x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0 and x.stride(2) == 1
 
     def fusable(self, x, swiglu=False):
@@ -213,7 +220,7 @@ class FusedDeltaLinear(nn.Module):
 
     def _dec_weight(self, x):
         """(weight, weight_tiled flag) for a decode launch: the tile-major copy when it exists and the launch has one row per tenant"""
-        if self.weight_tiled is not None and self.use_tiled and x.shape[1] == 1:
+        if self.weight_tiled is not None and (self.use_tiled or not self.dense_base) and x.shape[1] == 1:
             return self.weight_tiled, True
         return self.weight, False
 
@@ -232,21 +239,38 @@ class FusedDeltaLinear(nn.Module):
         ssq_out (decode, with residual): RMSNorm hand-off, producer side -- the launch also leaves the per-row partial sums of squares of the
         updated residual stream for the next launch (`handoff_producer_ok`), and with next_norm [T, N] + xw_out [T, 1, N] the copy of it
         pre-multiplied by the NEXT norm's weight.  out: caller-provided destination (tp.py: the all-reduce's peer-mapped buffer)."""
-        if self._decode_ok(x):
+        if self._decode_ok(x) and (self.dense_base or x.shape[1] == 1):
             w, wt = self._dec_weight(x)
             return binary_linear_decode(x, w, self.mask_packed, self.alpha, layout="packed", groups=self.groups,
                                         residual=residual, weight_tiled=wt, out_dtype=out_dtype, ssq_out=ssq_out,
                                         norm_weight=next_norm if ssq_out is not None else None, xw_out=xw_out, out=out, ssq_scale=ssq_scale,
                                         weight_scale=self._dec_scale(wt), **self._dec_q4(wt))
         assert ssq_out is None and xw_out is None
+        if not self.dense_base:
+            return self._forward_bytes(x, residual, out_dtype, out)
         return binary_linear(x, self.weight, self.mask, self.alpha, groups=self.groups, residual=residual, out_dtype=out_dtype, out=out)
+
+    def _forward_bytes(self, x, residual, out_dtype, out):
+        """dense_base=False, every launch the packed decode form does not take: ONE launch of the int8 GEMM on the bytes (one rounding, residual
+        included).  Rows the kernel cannot read in place (unaligned / strided) are copied first.  A single row per entry that is no decode
+        launch (a one-tenant view has no packed signs: `extend` by nothing, a one-row chunk) is presented twice -- row stride 0, nothing is
+        copied -- and row 0 of the two identical output rows is kept."""
+        if x.stride(2) != 1 or x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(1) % 8:
+            x = x.contiguous()
+        kw = dict(groups=self.groups, out_dtype=out_dtype, weight_scale=self.wscale)
+        if x.shape[1] != 1:
+            return binary_linear(x, self.weight_tiled, self.mask, self.alpha, residual=residual, out=out, **kw)
+        two = residual.repeat(1, 2, 1) if residual is not None else None
+        y = binary_linear(x.expand(-1, 2, -1), self.weight_tiled, self.mask, self.alpha, residual=two, **kw)[:, :1]
+        dst = residual if residual is not None else out
+        return y if dst is None else dst.copy_(y)
 
     def residual_norm_ok(self, x, residual):
         """forward_residual_norm can take this input: prefill rows on the fused GEMM's fast path, the residual stream contiguous, rows the norm
         kernels take whole (N % 8 == 0, N <= 8192)"""
         B, M, K = x.shape
-        N = self.weight.shape[0]
-        return (M > 16 and K % 64 == 0 and N % 8 == 0 and N <= 8192 and x.stride(2) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and
+        N = self.N
+        return (self.dense_base and M > 16 and K % 64 == 0 and N % 8 == 0 and N <= 8192 and x.stride(2) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and
                 x.stride(1) % 8 == 0 and residual.is_contiguous() and self.mask.shape[0] in (1, B))
 
     def forward_residual_norm(self, x, residual, norm_weight, eps):
@@ -256,7 +280,7 @@ class FusedDeltaLinear(nn.Module):
 
     def handoff_producer_ok(self, x):
         """this (residual) Linear can leave the sums of squares of its output behind: decode shape, one row per tenant, tile-major weight"""
-        return (self._decode_ok(x) and x.shape[1] == 1 and x.shape[0] <= 8 and self.weight.shape[0] % 16 == 0 and
+        return (self._decode_ok(x) and x.shape[1] == 1 and x.shape[0] <= 8 and self.N % 16 == 0 and
                 self.weight_tiled is not None and self.use_tiled)
 
     def handoff_consumer_ok(self, x, swiglu=False):
@@ -283,7 +307,7 @@ class FusedDeltaLinear(nn.Module):
     def swiglu_ok(self, x):
         """True when forward_swiglu can take this input: an interleaved gate|up pair at prefill size on the fused GEMM's fast path"""
         B, M, K = x.shape
-        return self.interleave8 and M > 16 and K % 64 == 0 and x.data_ptr() % 16 == 0 and x.stride(2) == 1 and \
+        return self.dense_base and self.interleave8 and M > 16 and K % 64 == 0 and x.data_ptr() % 16 == 0 and x.stride(2) == 1 and \
             x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0 and (self.mask.shape[0] in (1, B))
 
     def forward_swiglu(self, x):
@@ -300,6 +324,9 @@ class FusedDeltaLinear(nn.Module):
         v.weight, v.mask, v.alpha = self.weight, self.mask[t:t + 1], self.alpha[t:t + 1]
         v.alpha_pair = self.alpha_pair[t:t + 1] if self.alpha_pair is not None else None
         v.wscale = v.group_params = v.mask_packed = v.weight_tiled = None
+        v.dense_base, v.N, v.K = self.dense_base, self.N, self.K
+        if not self.dense_base:       # the bytes are the base: the view carries them (mask_packed stays None, so it never takes a decode launch)
+            v.weight_tiled, v.wscale = self.weight_tiled, self.wscale
         return v
 
     def check_tenant(self, t, masks, coeffs):
@@ -359,14 +386,14 @@ class FusedDeltaLinear(nn.Module):
 
     def column_alpha(self, t):
         """tenant t's scale of every stored output row, [N]"""
-        return self.alpha[t].repeat_interleave(self.weight.shape[0] // self.groups)
+        return self.alpha[t].repeat_interleave(self.N // self.groups)
 
     def linear_bytes(self):
         """algorithmic HBM bytes of one decode launch: base once (one byte per weight in base_int8 mode; half a byte plus the 4-byte group
         parameters in base_gptq4 mode) + every tenant's signs (activations / outputs / row scales are noise)"""
         if self.base_gptq4:
-            return self.weight.numel() // 2 + self.group_params.numel() * 4 + self.mask.numel() * 4
-        return self.weight.numel() * (1 if self.base_int8 else self.weight.element_size()) + self.mask.numel() * 4
+            return self.N * self.K // 2 + self.group_params.numel() * 4 + self.mask.numel() * 4
+        return self.N * self.K * (1 if self.base_int8 else self.weight.element_size()) + self.mask.numel() * 4
 
 
 class RopeSpec(collections.namedtuple("RopeSpec", "theta kind factor low_freq_factor high_freq_factor original_max_position_embeddings inv_freq")):
@@ -497,8 +524,10 @@ class TenantDecoder(nn.Module):
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
     def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None,
-                 kv_cache=None, kv_scales=None, sliding_window=None):
-        """sliding_window: None, or W >= 1 (Mistral-7B-v0.1 and its fine-tunes: 4096): the query at cache position i attends to the keys
+                 kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True):
+        """dense_base=False (with base_int8; not with base_gptq4): the delta Linears keep no 16-bit base -- the int8 bytes are the one resident
+        copy and every launch with more than one row per tenant runs the int8 GEMM on them (FusedDeltaLinear(dense_base=False)).
+        sliding_window: None, or W >= 1 (Mistral-7B-v0.1 and its fine-tunes: 4096): the query at cache position i attends to the keys
         i - W + 1 .. i only -- W keys including its own, the mask of Mistral's reference implementation and of current `transformers` -- in
         every attention branch (decode, ragged decode, whole-prompt prefill, prefill_chunk; the stock-op arms AND the same band into their
         masks), and the decode attention launch streams W rows however long the conversation is.  The KV cache stays linear, max_len rows.
@@ -547,6 +576,11 @@ class TenantDecoder(nn.Module):
         for sp in specs:
             rope_inv_freq(sp, hd_)                      # (refuses a record that is no spec, or frequencies of another head size)
         self._rope = specs                              # slot -> its spec (tenant_rope)
+        if not dense_base and base_gptq4:
+            raise ValueError("dense_base=False is the int8 base's mode: the 4-bit base has no kernel for more than one row per tenant")
+        if not dense_base and not base_int8:
+            raise ValueError("dense_base=False drops the 16-bit base weight: it needs base_int8=True")
+        self.dense_base = bool(dense_base)
         self.base_gptq4 = bool(base_gptq4)  # ... or a 4-bit GPTQ base (FusedDeltaLinear(base_gptq4=True)); lm_head, embeddings and norms stay 16-bit
         self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
         self.cfg, self.T, self.dtype, self.dev, self.eps = cfg, tenants, dtype, torch.device(device), eps
@@ -612,7 +646,7 @@ class TenantDecoder(nn.Module):
     # ---------------------------------------------------------------- construction
     @classmethod
     def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
-                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None, sliding_window=None):
+                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
         (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope, sliding_window: as in
@@ -621,7 +655,7 @@ class TenantDecoder(nn.Module):
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
         self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope, kv_cache=kv_cache,
-                   kv_scales=kv_scales, sliding_window=sliding_window)
+                   kv_scales=kv_scales, sliding_window=sliding_window, dense_base=dense_base)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -638,7 +672,7 @@ class TenantDecoder(nn.Module):
         def fused(*shapes, interleave8=False):
             parts = [delta_linear(o, i) for o, i in shapes]
             return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8, base_int8=base_int8,
-                                    base_gptq4=base_gptq4)
+                                    base_gptq4=base_gptq4, dense_base=dense_base)
 
         def per_tenant(*shape, scale=None):
             reps = 1 if shared_heads else tenants
@@ -670,7 +704,7 @@ class TenantDecoder(nn.Module):
         return b, self.T * self.lm_head.shape[1] * self.lm_head.shape[2] * self.lm_head.element_size()
 
     def linear_param_count(self):
-        return sum(l.qkv.weight.numel() + l.o.weight.numel() + l.gate_up.weight.numel() + l.down.weight.numel() for l in self.layers)
+        return sum(m.N * m.K for l in self.layers for m in (l.qkv, l.o, l.gate_up, l.down))
 
     # ---------------------------------------------------------------- forward
     def new_cache(self, length=None, kv_cache="decoder"):
@@ -992,7 +1026,7 @@ class TenantDecoder(nn.Module):
             pf, cur = self._pf_stream, torch.cuda.current_stream(x.device)
             pf.wait_stream(cur)
             with torch.cuda.stream(pf):
-                w_o = layer.o.weight_tiled if (layer.o.weight_tiled is not None and layer.o.use_tiled) else layer.o.weight
+                w_o = layer.o.weight_tiled if (layer.o.weight_tiled is not None and (layer.o.use_tiled or layer.o.weight is None)) else layer.o.weight
                 ops.cache_warm(w_o, layer.o.mask_packed)
         if ck.dtype == torch.float8_e4m3fn:
             a = self._layer_kv8(layer, qkv, cache, li, pos_idx, ragged)
@@ -1362,7 +1396,7 @@ class TenantDecoder(nn.Module):
         v = views.get(t)
         if v is None:
             v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4,
-                              rope=self._rope[t], kv_cache=self.kv_cache, sliding_window=self.sliding_window)
+                              rope=self._rope[t], kv_cache=self.kv_cache, sliding_window=self.sliding_window, dense_base=self.dense_base)
             # the parent's table, or the tenant's rows of it: a slice of the storage load_tenant(rope=) rewrites in place
             v.cos, v.sin = (self.cos[t], self.sin[t]) if self.rope_per_tenant else (self.cos, self.sin)
             for layer in self.layers:
