@@ -113,7 +113,8 @@ def delta_bmm(a, b, *, out=None, out_dtype=None, round_mode=1, alpha=None, accum
     return out
 
 
-def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=None, out=None, weight_scale=None):
+def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=None, out=None, weight_scale=None, group_params=None,
+                  group_size=128):
     """Fused 16-bit base + 1-bit delta Linear:  y[i] = x[i] . weight^T + alpha[i] * (x[i] . S[i])  in ONE launch.
 
     x: (B, M, K); weight: (N, K) rows k-contiguous; mask: (B or 1, K/32, N) int32; alpha: fp32 (B or 1, groups).
@@ -128,7 +129,14 @@ def binary_linear(x, weight, mask, alpha, *, out_dtype=None, groups=1, residual=
     decode copy, the one resident form of an int8 base) and weight_scale = quant.weight_scale(SCB) (fp32 [N]):
     y = weight_scale * (x . CB^T) + alpha * (x . S), the scale on the finished fp32 base sum; `residual` is added before the one rounding.
     ValueError for an int8 weight without a scale (or a scale with a 16-bit weight), M == 1 and shapes outside the envelope.
+    4-BIT GPTQ base weight (bd_binary_linear_q4; M >= 2, N % 16 == 0, K % 128 == 0): weight = quant.tile_weight_gptq4(qweight) (int32 [N, K/8],
+    the decode copy, the one resident form of a 4-bit base), group_params = quant.pack_gptq4_params(qzeros, scales) (int32
+    [N/16, K/group_size, 16]) and group_size a multiple of 128 that divides K:  y = x . Wdq^T + alpha * (x . S)  with Wdq bit for bit
+    quant.dequantize_base_gptq4(...) in x.dtype, formed in registers; `residual` is added before the one rounding.  ValueError for an int32
+    weight without group_params (or group_params with another weight, or together with weight_scale), M == 1 and shapes outside the envelope.
     """
+    if weight.dtype == torch.int32 or group_params is not None:
+        return _binary_linear_q4(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_scale, group_params, group_size)
     if weight.dtype == torch.int8 or weight_scale is not None:
         return _binary_linear_w8(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_scale)
     require_gpu(x, weight, mask, alpha, residual, out)
@@ -213,6 +221,55 @@ def _binary_linear_w8(x, weight, mask, alpha, out_dtype, groups, residual, out, 
         check(lib().bd_binary_linear_w8(ptr(x), ptr(weight), ptr(weight_scale), ptr(mask), ptr(alpha), ptr(y), B, M, N, K, x.stride(0), x.stride(1),
                                         sPb, sAlb, groups, y.stride(0), y.stride(1), DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype],
                                         1 if residual is not None else 0, stream_ptr()), "binary_linear_w8")
+    return y
+
+
+def _binary_linear_q4(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_scale, group_params, group_size):
+    """binary_linear's 4-bit form: one launch of bd_binary_linear_q4 over the tile-major nibbles.  The refusals come first (they need no device)."""
+    assert x.dim() == 3 and mask.dim() == 3 and weight.dim() == 2
+    if weight.dtype != torch.int32:
+        raise ValueError("group_params goes with the int32 tile-major nibbles (quant.tile_weight_gptq4), not with a %s weight" % weight.dtype)
+    if weight_scale is not None:
+        raise ValueError("weight_scale is the int8 base's; group_params carries the 4-bit base's scales: pass one of them")
+    if group_params is None:
+        raise ValueError("an int32 (4-bit GPTQ) weight needs group_params = quant.pack_gptq4_params(qzeros, scales)")
+    B, M, K = x.shape
+    N, G = weight.shape[0], int(group_size)
+    if M == 1:
+        raise ValueError("one row per batch entry is a decode launch: binary_linear_decode(..., group_params=...)")
+    if N % 16 or K % 128 or K == 0 or N == 0 or weight.shape[1] * 8 != K or not weight.is_contiguous():
+        raise ValueError("4-bit base: a contiguous [N, K/8] tile-major weight with N % 16 == 0 and K % 128 == 0 is required")
+    if G < 128 or G % 128 or K % G:
+        raise ValueError("4-bit base: group_size must be a multiple of 128 that divides K (a 128-k stage lies inside one group), got %d" % G)
+    if group_params.dtype != torch.int32 or tuple(group_params.shape) != (N // 16, K // G, 16) or not group_params.is_contiguous():
+        raise ValueError("group_params: contiguous int32 [N/16, K/group_size, 16] = [%d, %d, 16]" % (N // 16, K // G))
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.stride(2) != 1 or x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(1) % 8:
+        raise ValueError("4-bit base: fp16 / bf16 activations with 16-byte aligned, k-contiguous rows are required")
+    if weight.data_ptr() % 16 or group_params.data_ptr() % 16 or N % groups or K // 128 >= 65536:
+        raise ValueError("4-bit base: 16-byte aligned weight and group_params, groups dividing N, K < 2^23")
+    require_gpu(x, weight, mask, alpha, residual, out, group_params)
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and mask.shape[1] * 32 == K and mask.shape[2] == N and mask.shape[0] in (1, B)
+    out_dtype = out_dtype or x.dtype
+    alpha = alpha.detach()
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    alpha = alpha.reshape(-1, groups)
+    assert alpha.shape[0] in (1, B)
+    sPb = 0 if (mask.shape[0] == 1 and B > 1) else mask.stride(0)
+    sAlb = 0 if alpha.shape[0] == 1 else groups
+    if residual is not None:
+        assert out is None, "out= and residual= are exclusive"
+        assert residual.shape == (B, M, N) and residual.dtype == out_dtype and residual.stride(2) == 1
+        y = residual
+    elif out is not None:
+        assert out.shape == (B, M, N) and out.dtype == out_dtype and out.stride(2) == 1 and out.device == x.device
+        y = out
+    else:
+        y = torch.empty((B, M, N), device=x.device, dtype=out_dtype)
+    with torch.cuda.device(x.device):
+        check(lib().bd_binary_linear_q4(ptr(x), ptr(weight), ptr(group_params), G, ptr(mask), ptr(alpha), ptr(y), B, M, N, K, x.stride(0),
+                                        x.stride(1), sPb, sAlb, groups, y.stride(0), y.stride(1), DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype],
+                                        1 if residual is not None else 0, stream_ptr()), "binary_linear_q4")
     return y
 
 

@@ -16,6 +16,7 @@
 #include "bd_gemm_fx.h"
 #include "bd_gemm_w4.h"
 #include "bd_gemm_w8.h"
+#include "bd_gemm_q4.h"
 #include "bd_gemv.h"
 #include "bd_gemv_stream.h"
 #include "bd_gemv_rows.h"
@@ -50,6 +51,7 @@ static thread_local int g_tail_split = env_int("BD_TAIL_SPLIT", 1) ? 1 : 0;     
 // delta_rows_kernel A/B hook (environment only): bits 1-2 = masks per block forced to 1 / 2 / 4 (value 1 / 2 / 3), bit 4 = never chosen automatically,
 // bit 5 = 64-column super-tiles even when they leave CUs idle, bit 6 = 32-column super-tiles always
 static thread_local int g_rows_tune = env_int("BD_ROWS_TUNE", 0);
+static thread_local int g_q4_tiles = env_int("BD_Q4_TILES", 0);                     // gemm_q4_kernel A/B hook (environment only): 1 / 2 = column tiles per wave forced
 static thread_local int g_norm_rows_min = env_int("BD_NORM_ROWS_MIN", 64);           // bd_srv_rmsnorm: rows from which the wave-per-row kernel runs (A/B hook)
 static thread_local int g_attn_depth = env_int("BD_ATTN_DEPTH", 0);                 // decode attention K / V ring depth: 0 = by cache length, 2, 4 (A/B hook)
 static thread_local int g_rows_shared_min = env_int("BD_ROWS_SHARED_MIN", 1);       // shared mask: rows from which the kernel is chosen automatically
@@ -1496,6 +1498,36 @@ template <int DT> static int launch_gemm_w8(const W8Params& p, const W8Plan& pl,
     return launch_status();
 }
 
+// ---- bd_binary_linear_q4: the 4-bit GPTQ base at M >= 2 (gemm_q4_kernel, bd_gemm_q4.h).  The whole dispatch rule: a workgroup covers 16 rb rows x
+// 16 nw tw columns (tw column tiles per wave).  M picks the rows and the waves exactly as w8_plan does -- up to 64 rows the 4-wave group, above
+// the 8-wave one with 8 row blocks.  Tiles per wave: Q4_TW_LARGE above 64 rows, where a launch has workgroups to spare and the shared X stage is
+// what is saved; Q4_TW_SMALL up to 64 rows, where two tiles per wave halve an already short list of workgroups (N / 128 x B).  Both constants
+// are the measured winners of the two-tile A/B (profiles/q4_prefill.txt); BD_Q4_TILES=1 / 2 forces one form for that measurement.
+constexpr int Q4_TW_LARGE = 2, Q4_TW_SMALL = 1;
+struct Q4Plan { int rb, nw, tw, tiles_m, groups; };
+inline Q4Plan q4_plan(int M, int N) {
+    Q4Plan pl;
+    pl.rb = M <= 16 ? 1 : M <= 32 ? 2 : M <= 64 ? 4 : 8;
+    pl.nw = pl.rb == 8 ? 8 : 4;
+    pl.tw = (g_q4_tiles == 1 || g_q4_tiles == 2) ? g_q4_tiles : pl.rb == 8 ? Q4_TW_LARGE : Q4_TW_SMALL;
+    pl.tiles_m = (M + 16 * pl.rb - 1) / (16 * pl.rb);
+    pl.groups = (N + 16 * pl.nw * pl.tw - 1) / (16 * pl.nw * pl.tw);
+    return pl;
+}
+template <int DT, int TW> static int launch_gemm_q4_tw(const Q4Params& p, const Q4Plan& pl, int B, hipStream_t st) {
+    const dim3 grid((unsigned)(pl.tiles_m * pl.groups), (unsigned)B), block(64 * pl.nw);
+    switch (pl.rb) {
+        case 1: hipLaunchKernelGGL((gemm_q4_kernel<DT, 1, 4, TW>), grid, block, 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemm_q4_kernel<DT, 2, 4, TW>), grid, block, 0, st, p); break;
+        case 4: hipLaunchKernelGGL((gemm_q4_kernel<DT, 4, 4, TW>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((gemm_q4_kernel<DT, 8, 8, TW>), grid, block, 0, st, p); break;
+    }
+    return launch_status();
+}
+template <int DT> static int launch_gemm_q4(const Q4Params& p, const Q4Plan& pl, int B, hipStream_t st) {
+    return pl.tw == 2 ? launch_gemm_q4_tw<DT, 2>(p, pl, B, st) : launch_gemm_q4_tw<DT, 1>(p, pl, B, st);
+}
+
 // `q` arrives with what the entry point fuses around the Linear or says about its base weight, filled by name: norm_w / sNw / eps / epilogue,
 // ssq_in / ssq_out / xw_out, pn_*, and wscale (int8: its presence is the signal) or q4p / q4_group (4-bit); everything else is set here.
 static int binary_linear_impl(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B, int M,
@@ -1683,6 +1715,32 @@ extern "C" int bd_binary_linear_w8(const void* X, const int8_t* W8, const float*
     p.out_f32 = out_dtype == BD_F32; p.accumulate = accumulate ? 1 : 0;
     p.vec = ((uintptr_t)Y % (p.out_f32 ? 16 : 8) == 0) && sYb % 4 == 0 && sYm % 4 == 0;
     return dtype == BD_BF16 ? launch_gemm_w8<DT_BF16>(p, pl, B, (hipStream_t)stream) : launch_gemm_w8<DT_F16>(p, pl, B, (hipStream_t)stream);
+}
+
+extern "C" int bd_binary_linear_q4(const void* X, const int32_t* W4, const uint32_t* qparams, int group_size, const int32_t* P, const float* alpha,
+                                   void* Y, int B, int M, int N, int K, int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                                   int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, void* stream) {
+    if (B < 0 || M < 0 || N < 0 || K < 0) return BD_E_BAD_SHAPE;
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (out_dtype != dtype && out_dtype != BD_F32) return BD_E_BAD_DTYPE;
+    if (B == 0 || M == 0) return BD_OK;
+    if (!X || !W4 || !qparams || !P || !alpha || !Y) return BD_E_NULL;
+    if (M < 2 || N < 16 || N % 16 || K < 128 || K % 128 || B > 65535) return BD_E_BAD_SHAPE;      // (M == 1: bd_binary_linear_decode_q4)
+    if (group_size < 128 || group_size % 128 || K % group_size) return BD_E_BAD_SHAPE;            // (a 128-k stage lies inside one group)
+    if (K / 128 >= 65536) return BD_E_BAD_SHAPE;                                                  // (the magic division is exact below that)
+    if (!aligned16(X) || sXb % 8 || sXm % 8 || !aligned16(W4) || !aligned16(qparams) || sPb < 0 || sAlb < 0) return BD_E_BAD_SHAPE;
+    if (G < 1 || N % G) return BD_E_BAD_GROUPS;
+    const Q4Plan pl = q4_plan(M, N);
+    if ((int64_t)pl.tiles_m * pl.groups > 0x7fffffffll) return BD_E_BAD_SHAPE;
+    Q4Params p{};
+    p.X = (const unsigned short*)X; p.W4 = (const uint32_t*)W4; p.qp = qparams; p.P = (const uint32_t*)P; p.alpha = alpha; p.C = Y;
+    p.M = M; p.N = N; p.K = K; p.gsz = N / G; p.tiles_m = pl.tiles_m;
+    const uint32_t per = (uint32_t)(group_size / 128);
+    p.ngrp = (uint32_t)(K / group_size); p.magic = per > 1 ? (uint32_t)((1ull << 32) / per) + 1u : 0u;
+    p.sXb = sXb; p.sXm = sXm; p.sPb = sPb; p.sAlb = sAlb; p.sCb = sYb; p.sCm = sYm;
+    p.out_f32 = out_dtype == BD_F32; p.accumulate = accumulate ? 1 : 0;
+    p.vec = ((uintptr_t)Y % (p.out_f32 ? 16 : 8) == 0) && sYb % 4 == 0 && sYm % 4 == 0;
+    return dtype == BD_BF16 ? launch_gemm_q4<DT_BF16>(p, pl, B, (hipStream_t)stream) : launch_gemm_q4<DT_F16>(p, pl, B, (hipStream_t)stream);
 }
 
 extern "C" int bd_binary_linear_residual(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int B,

@@ -137,11 +137,16 @@ class FusedDeltaLinear(nn.Module):
         group size from the checkpoint (K / scales.shape[0]) and `dtype` says what the dequantised weight is cast to.  from_gptq4 spells it.
         dense_base=False (with base_int8): the 16-bit `weight` is NOT kept (`self.weight is None`) -- the int8 tile-major bytes are the one
         resident copy of the base, and every launch with more than one row per tenant runs bd_binary_linear_w8 on them (prefill, extend,
-        chunks, scoring); the fused SwiGLU / residual + norm prefill forms are not offered, the layer takes its separate launches."""
+        chunks, scoring); the fused SwiGLU / residual + norm prefill forms are not offered, the layer takes its separate launches.
+        base_gptq4="only": the same for the 4-bit base -- the tile-major nibbles and the group parameters are the one resident copy, the
+        dequantised 16-bit weight is neither built nor kept, and those launches run bd_binary_linear_q4.  It needs the decode copies
+        (N % 16 == 0, K % 128 == 0, group_size % 128 == 0, at most 16 tenants): ValueError otherwise.  Internally it is dense_base = False."""
         super().__init__()
         if not dense_base and not base_int8:
             raise ValueError("dense_base=False drops the 16-bit base weight: it needs base_int8=True (the int8 bytes are then the only copy)")
-        self.dense_base = bool(dense_base)
+        if isinstance(base_gptq4, str) and base_gptq4 != "only":
+            raise ValueError('base_gptq4: False, True or "only", got %r' % (base_gptq4,))
+        self.dense_base = bool(dense_base) and base_gptq4 != "only"
         self.base_int8 = bool(base_int8)
         self.base_gptq4 = bool(base_gptq4)
         self.group_size = int(group_size)
@@ -158,6 +163,12 @@ class FusedDeltaLinear(nn.Module):
         self.widths = widths
         self.interleave8 = bool(interleave8)
         weight, mask = torch.cat(weights, 0), torch.cat(masks, 2)                               # [N, K], [T, K/32, N]
+        if base_gptq4 == "only":
+            K = qw.shape[0] * 8 if qw is not None else mask.shape[1] * 32
+            if mask.shape[2] % 16 or K % 128 or self.group_size % 128 or K % self.group_size or mask.shape[0] > 16 or not decode_copies:
+                raise ValueError('base_gptq4="only" needs the decode copies, they are the base: N %% 16 == 0, K %% 128 == 0, group_size a multiple '
+                                 "of 128 that divides K, at most 16 tenants (N = %d, K = %d, group_size = %d, %d tenants)"
+                                 % (mask.shape[2], K, self.group_size, mask.shape[0]))
         perm = fused_perm(widths, self.interleave8, weight.device)
         if perm is not None:
             weight, mask = weight[perm], mask[:, :, perm]
@@ -177,8 +188,8 @@ class FusedDeltaLinear(nn.Module):
             if gptq4 is None:
                 qw, qz, sc = quantize_base_gptq4(weight, self.group_size)
             assert self.group_size % 128 == 0 and (qw.shape[0] * 8) % self.group_size == 0, "group_size: a multiple of 128 that divides K"
-            weight = dequantize_base_gptq4(qw, qz, sc, weight.dtype)
-            self.register_buffer("group_params", pack_gptq4_params(qz, sc) if weight.shape[0] % 16 == 0 else None)
+            weight = dequantize_base_gptq4(qw, qz, sc, weight.dtype) if self.dense_base else None        # (never built when it is not kept)
+            self.register_buffer("group_params", pack_gptq4_params(qz, sc) if mask.shape[2] % 16 == 0 else None)
         else:
             self.group_params = None
         self.N, self.K = mask.shape[2], mask.shape[1] * 32
@@ -202,10 +213,12 @@ class FusedDeltaLinear(nn.Module):
             self.register_buffer("weight_tiled", tile_weight(self.weight) if tiled else None)
 
     @classmethod
-    def from_gptq4(cls, triples, masks, coeffs, dtype=torch.float16, interleave8=False, decode_copies=True):
+    def from_gptq4(cls, triples, masks, coeffs, dtype=torch.float16, interleave8=False, decode_copies=True, only=False):
         """A fused Linear over the projections of a GPTQ checkpoint: triples = [(qweight int32 [K/8, N_i], qzeros int32 [K/G, N_i/8], scales fp16
-        [K/G, N_i]), ...]; masks / coeffs as in __init__.  The group size is the checkpoint's (K / scales.shape[0])."""
-        return cls(None, masks, coeffs, interleave8=interleave8, decode_copies=decode_copies, base_gptq4=True, gptq4=triples, dtype=dtype)
+        [K/G, N_i]), ...]; masks / coeffs as in __init__.  The group size is the checkpoint's (K / scales.shape[0]).  only=True: the nibbles
+        are the one resident copy (base_gptq4="only"); `dtype` then only says which activations the module serves."""
+        return cls(None, masks, coeffs, interleave8=interleave8, decode_copies=decode_copies, base_gptq4="only" if only else True, gptq4=triples,
+                   dtype=dtype)
 
     def _decode_ok(self, x):
         B, M, K = x.shape
@@ -251,13 +264,15 @@ class FusedDeltaLinear(nn.Module):
         return binary_linear(x, self.weight, self.mask, self.alpha, groups=self.groups, residual=residual, out_dtype=out_dtype, out=out)
 
     def _forward_bytes(self, x, residual, out_dtype, out):
-        """dense_base=False, every launch the packed decode form does not take: ONE launch of the int8 GEMM on the bytes (one rounding, residual
+        """No 16-bit base (int8 with dense_base=False, base_gptq4="only"), every launch the packed decode form does not take: ONE launch of the
+        int8 / 4-bit GEMM on the decode copy (bd_binary_linear_w8 with weight_scale=, bd_binary_linear_q4 with group_params=; one rounding, residual
         included).  Rows the kernel cannot read in place (unaligned / strided) are copied first.  A single row per entry that is no decode
         launch (a one-tenant view has no packed signs: `extend` by nothing, a one-row chunk) is presented twice -- row stride 0, nothing is
         copied -- and row 0 of the two identical output rows is kept."""
         if x.stride(2) != 1 or x.data_ptr() % 16 or x.stride(0) % 8 or x.stride(1) % 8:
             x = x.contiguous()
-        kw = dict(groups=self.groups, out_dtype=out_dtype, weight_scale=self.wscale)
+        kw = dict(groups=self.groups, out_dtype=out_dtype)
+        kw.update(dict(group_params=self.group_params, group_size=self.group_size) if self.base_gptq4 else dict(weight_scale=self.wscale))
         if x.shape[1] != 1:
             return binary_linear(x, self.weight_tiled, self.mask, self.alpha, residual=residual, out=out, **kw)
         two = residual.repeat(1, 2, 1) if residual is not None else None
@@ -326,7 +341,7 @@ class FusedDeltaLinear(nn.Module):
         v.wscale = v.group_params = v.mask_packed = v.weight_tiled = None
         v.dense_base, v.N, v.K = self.dense_base, self.N, self.K
         if not self.dense_base:       # the bytes are the base: the view carries them (mask_packed stays None, so it never takes a decode launch)
-            v.weight_tiled, v.wscale = self.weight_tiled, self.wscale
+            v.weight_tiled, v.wscale, v.group_params = self.weight_tiled, self.wscale, self.group_params
         return v
 
     def check_tenant(self, t, masks, coeffs):
@@ -527,6 +542,8 @@ class TenantDecoder(nn.Module):
                  kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True):
         """dense_base=False (with base_int8; not with base_gptq4): the delta Linears keep no 16-bit base -- the int8 bytes are the one resident
         copy and every launch with more than one row per tenant runs the int8 GEMM on them (FusedDeltaLinear(dense_base=False)).
+        base_gptq4="only": the same for the 4-bit base -- the nibbles and group parameters are the one resident copy, those launches run the
+        4-bit GEMM (FusedDeltaLinear(base_gptq4="only")); base_gptq4=True keeps the dequantised 16-bit weight next to them, as before.
         sliding_window: None, or W >= 1 (Mistral-7B-v0.1 and its fine-tunes: 4096): the query at cache position i attends to the keys
         i - W + 1 .. i only -- W keys including its own, the mask of Mistral's reference implementation and of current `transformers` -- in
         every attention branch (decode, ragged decode, whole-prompt prefill, prefill_chunk; the stock-op arms AND the same band into their
@@ -577,10 +594,13 @@ class TenantDecoder(nn.Module):
             rope_inv_freq(sp, hd_)                      # (refuses a record that is no spec, or frequencies of another head size)
         self._rope = specs                              # slot -> its spec (tenant_rope)
         if not dense_base and base_gptq4:
-            raise ValueError("dense_base=False is the int8 base's mode: the 4-bit base has no kernel for more than one row per tenant")
+            raise ValueError("dense_base=False is the int8 base's switch: the 4-bit base drops its 16-bit weight with base_gptq4=\"only\"")
         if not dense_base and not base_int8:
             raise ValueError("dense_base=False drops the 16-bit base weight: it needs base_int8=True")
+        if isinstance(base_gptq4, str) and base_gptq4 != "only":
+            raise ValueError('base_gptq4: False, True or "only", got %r' % (base_gptq4,))
         self.dense_base = bool(dense_base)
+        self.gptq4_only = base_gptq4 == "only"     # the delta Linears keep no 16-bit base either: the nibbles are the one copy
         self.base_gptq4 = bool(base_gptq4)  # ... or a 4-bit GPTQ base (FusedDeltaLinear(base_gptq4=True)); lm_head, embeddings and norms stay 16-bit
         self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
         self.cfg, self.T, self.dtype, self.dev, self.eps = cfg, tenants, dtype, torch.device(device), eps
@@ -1395,7 +1415,8 @@ class TenantDecoder(nn.Module):
         views = self._tenant_views
         v = views.get(t)
         if v is None:
-            v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8, base_gptq4=self.base_gptq4,
+            v = TenantDecoder(self.cfg, 1, self.dev, self.dtype, max_len=self.max_len, eps=self.eps, base_int8=self.base_int8,
+                              base_gptq4="only" if self.gptq4_only else self.base_gptq4,
                               rope=self._rope[t], kv_cache=self.kv_cache, sliding_window=self.sliding_window, dense_base=self.dense_base)
             # the parent's table, or the tenant's rows of it: a slice of the storage load_tenant(rope=) rewrites in place
             v.cos, v.sin = (self.cos[t], self.sin[t]) if self.rope_per_tenant else (self.cos, self.sin)

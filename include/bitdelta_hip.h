@@ -210,6 +210,22 @@ int bd_binary_linear_w8(const void* X, const int8_t* W8, const float* wscale, co
                         int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
                         int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, void* stream);
 
+/* The fused Linear over the 4-BIT GPTQ base weight for M >= 2 rows per batch entry (prefill, extend, prefill chunks, scoring): the formula and
+ * the operands of bd_binary_linear_decode_q4 -- W4 is the SAME tile-major nibble copy (quant.tile_weight_gptq4) and qparams the same packed
+ * (scale, 1024 + z) dwords [N/16][K/group_size][16] (quant.pack_gptq4_params), so a 4-bit model keeps one copy of its base --
+ *     Y[b,m,n] = round( sum_k X[b,m,k] Wdq[n,k]  +  alpha[b, g(n)] * sum_k X[b,m,k] S_b[k,n]  [+ Y_in[b,m,n]] )
+ *     Wdq[n,k] = dtype( fp16( (q[n,k] - z[k / group_size, n]) * scale[k / group_size, n] ) )     (the reference's dequantised weight, bit for bit)
+ * fp32 accumulation, one rounding to out_dtype (dtype or BD_F32); accumulate = 1 adds Y's previous contents before that rounding.
+ *   P: sign words in the reference layout [B or 1, K/32, N] (sPb == 0 broadcasts one mask); alpha fp32 [B or 1, G] (sAlb == 0 broadcasts).
+ * One launch of gemm_q4_kernel (csrc/bd_gemm_q4.h): no workspace, no atomics, capturable in a graph, a pure function of its inputs.
+ * Envelope: M >= 2 (M == 1 is the decode entry's), N % 16 == 0, K % 128 == 0, K / 128 < 65536, group_size a multiple of 128 that divides K,
+ * 16-byte aligned X rows, W4 and qparams, B <= 65535; anything else returns BD_E_BAD_SHAPE (G < 1 or N % G: BD_E_BAD_GROUPS).  B == 0 or
+ * M == 0 returns BD_OK.  Arguments are validated before any device work. */
+int bd_binary_linear_q4(const void* X, const int32_t* W4, const uint32_t* qparams, int group_size, const int32_t* P, const float* alpha, void* Y,
+                        int B, int M, int N, int K,
+                        int64_t sXb, int64_t sXm, int64_t sPb, int64_t sAlb, int G,
+                        int64_t sYb, int64_t sYm, int dtype, int out_dtype, int accumulate, void* stream);
+
 /* the same Linear with the residual connection folded into its epilogue:  Y[b] = Y_in[b] + X[b] . W^T + alpha * (X[b] . S[b])
  * -- the `hidden = residual + o_proj(...)` / `+ down_proj(...)` of the decoder layers that call the reference's modules.
  * Decode shapes (M <= 16, B*M <= 64): fp32 sum, one rounding.  M > 16 on the fused GEMM's fast path (K % 64 == 0, 16-byte aligned
