@@ -50,6 +50,7 @@ SIGNATURES = {
                                          _i64, _i64, _ci, _ci, _ci, _vp, _i64, ctypes.c_float, _ci, _vp, _vp, _vp, _vp]),
     "bd_binary_linear_decode_q4": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _ci,
                                          _i64, _i64, _ci, _ci, _ci, _vp, _i64, ctypes.c_float, _ci, _vp, _vp, _vp, _vp]),
+    "bd_binary_linear_decode_wide": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _i64, _i64, _ci, _i64, _ci, _ci, _ci, _vp]),
     "bd_binary_linear_w8": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _ci, _i64, _i64, _ci, _ci, _ci, _vp]),
     "bd_binary_linear_q4": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _i64, _i64, _i64, _i64, _ci, _i64, _i64, _ci, _ci, _ci, _vp]),
     "bd_srv_cache_warm": (_ci, [_vp, _i64, _vp, _i64, _ci, _vp]),

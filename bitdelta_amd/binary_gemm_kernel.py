@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import DTYPE_CODE, WORD_DTYPE, check, lib, ptr, require_gpu, stream_ptr, workspace
 
 __all__ = ["pack", "unpack", "binary_matmul", "binary_bmm", "delta_bmm", "binary_linear", "binary_linear_residual_norm", "tenant_linear", "tile_masks",
-           "pack_decode_masks", "load_decode_masks", "binary_linear_decode", "decode_shape_ok"]
+           "pack_decode_masks", "pack_decode_masks_wide", "load_decode_masks", "binary_linear_decode", "decode_shape_ok"]
 
 
 def pack(x, n_bits=32):
@@ -378,6 +378,60 @@ def pack_decode_masks(mask):
     return out.contiguous()
 
 
+def pack_decode_masks_wide(mask):
+    """Sign words [T, K/32, N] (reference / diff.pt layout), T <= 64, in the WIDE decode layout of bd_binary_linear_decode_wide:
+    int32 [ceil(T/16), ceil(N/16), ceil(K/128), 4, 16, 16].  Row group g is byte for byte pack_decode_masks(mask[16 g : 16 g + 16]) with
+    t_pad = 16 (the last group zero-padded), so load_decode_masks(src, packed=wide[g], slot=t % 16) replaces tenant t = 16 g + slot in
+    place."""
+    assert mask.dim() == 3 and mask.dtype == torch.int32
+    T = mask.shape[0]
+    assert 1 <= T <= 64, "the wide decode layout holds 1 .. 64 tenants per call"
+    groups = []
+    for g in range((T + 15) // 16):
+        p = pack_decode_masks(mask[16 * g:16 * g + 16])
+        groups.append(torch.nn.functional.pad(p, (0, 16 - p.shape[4])) if p.shape[4] != 16 else p)
+    return torch.stack(groups).contiguous()
+
+
+def _binary_linear_decode_wide(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_tiled, refused):
+    """layout="wide" of binary_linear_decode: one launch of bd_binary_linear_decode_wide"""
+    for name, given in refused:
+        if given:
+            raise ValueError("layout=\"wide\" (17 .. 64 tenants in one launch) does not take %s" % name)
+    if not weight_tiled:
+        raise ValueError("layout=\"wide\" reads the tile-major base weight: pass tile_weight(W), weight_tiled=True")
+    if x.dim() != 3 or x.shape[1] != 1:
+        raise ValueError("layout=\"wide\" serves one row per tenant: x is (T, 1, K)")
+    if weight.dtype in (torch.int8, torch.int32):
+        raise ValueError("layout=\"wide\" does not take an int8 / 4-bit base weight")
+    require_gpu(x, weight, mask, alpha, residual, out)
+    T, _, K = x.shape
+    N = weight.shape[0]
+    assert 1 <= T <= 64 and N % 16 == 0 and K % 128 == 0 and weight.shape == (N, K) and weight.is_contiguous() and weight.dtype == x.dtype
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and tuple(mask.shape) == ((T + 15) // 16, N // 16, K // 128, 4, 16, 16)
+    assert x.stride(2) == 1
+    out_dtype = out_dtype or x.dtype
+    alpha = alpha.detach()
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    alpha = alpha.reshape(-1, groups)
+    assert alpha.shape[0] in (1, T)
+    if residual is not None:
+        assert out is None and residual.shape == (T, 1, N) and residual.dtype == out_dtype and residual.stride(2) == 1
+        y = residual
+    elif out is not None:
+        assert out.shape == (T, 1, N) and out.dtype == out_dtype and out.stride(2) == 1
+        y = out
+    else:
+        y = torch.empty((T, 1, N), device=x.device, dtype=out_dtype)
+    with torch.cuda.device(x.device):
+        check(lib().bd_binary_linear_decode_wide(ptr(x), ptr(weight), ptr(mask), ptr(alpha), ptr(y), T, N, K, x.stride(0) if T > 1 else K,
+                                                 0 if alpha.shape[0] == 1 else groups, groups, y.stride(0) if T > 1 else N,
+                                                 DTYPE_CODE[x.dtype], DTYPE_CODE[out_dtype], 1 if residual is not None else 0,
+                                                 stream_ptr()), "binary_linear_decode_wide")
+    return y
+
+
 def load_decode_masks(src, *, mask=None, packed=None, slot=0, col_off=0, col_blk=None, col_stride=0):
     """Write ONE tenant's sign words of one projection, src [K/32, N_src] int32 (reference / diff.pt layout; rows may be strided), IN PLACE into
     packed : slot `slot` of a whole tenant set's pack_decode_masks(...) result, [ceil(Nf/16), ceil(KW/4), 4, 16, t_pad], and / or
@@ -451,7 +505,15 @@ def binary_linear_decode(x, weight, mask, alpha, *, layout="tile", out_dtype=Non
     4-BIT GPTQ base weight (bd_binary_linear_decode_q4; packed layout, M == 1, N % 16 == 0, K % 128 == 0, group_size % 128 == 0):
       weight = quant.tile_weight_gptq4(qweight) (int32 [N, K/8], tile-major nibbles: there is no row-major 4-bit form), group_params =
       quant.pack_gptq4_params(qzeros, scales) (int32 [N/16, K/group_size, 16]); every keyword above keeps its meaning.  The nibbles are
-      dequantised in registers to exactly quant.dequantize_base_gptq4(...): the result is the 16-bit launch's on that weight."""
+      dequantised in registers to exactly quant.dequantize_base_gptq4(...): the result is the 16-bit launch's on that weight.
+    layout "wide" (bd_binary_linear_decode_wide): mask = pack_decode_masks_wide(...) (ceil(T/16), N/16, K/128, 4, 16, 16), x (T, 1, K) with
+      up to 64 tenants, weight = tile_weight(W) with weight_tiled=True, alpha (T or 1, groups); residual / out / out_dtype keep their meaning.
+      One launch that streams W once; every other keyword (norm_weight, swiglu, the hand-off, an int8 / 4-bit base) raises ValueError."""
+    if layout == "wide":
+        return _binary_linear_decode_wide(x, weight, mask, alpha, out_dtype, groups, residual, out, weight_tiled,
+                                          (("norm_weight", norm_weight is not None), ("swiglu", swiglu), ("ssq_in", ssq_in is not None),
+                                           ("ssq_out", ssq_out is not None), ("xw_out", xw_out is not None),
+                                           ("weight_scale", weight_scale is not None), ("group_params", group_params is not None)))
     q4 = weight.dtype == torch.int32
     if q4 or group_params is not None:      # (refused here, before anything looks at a device)
         if not q4:

@@ -20,6 +20,7 @@
 #include "bd_gemv.h"
 #include "bd_gemv_stream.h"
 #include "bd_gemv_rows.h"
+#include "bd_gemv_wide.h"
 #ifdef BD_AB_VARIANTS
 #include "../../tests/native/ab/bd_gemv_ring.h"     // LDS-DMA loader / consumer decode kernel: lost its A/B (profiles/r04_decode_ring_ab.txt)
 #endif
@@ -1693,6 +1694,46 @@ extern "C" int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, cons
     e.q4p = qparams; e.q4_group = group_size;
     return binary_linear_impl(X, W4, P, alpha, Y, B, M, N, K, sXb, sXm, /* ldw: tile-major */ 0, sPb, sAlb, G, sYb, sYm, dtype, out_dtype,
                               accumulate, 2, t_pad, nullptr, 0, stream, e);
+}
+
+// ---- bd_binary_linear_decode_wide: 17..64 tenants in one launch (gemv_wide_kernel, bd_gemv_wide.h).  The whole plan: T picks the number of
+// 16-tenant row groups (the kernel's NG: two accumulators per group), N the grid -- one block of 4 waves per 16-column tile, two blocks per CU.
+struct WidePlan { int ng; unsigned grid; };
+inline WidePlan wide_plan(int T, int N) { return WidePlan{(T + 15) / 16, (unsigned)(N / 16)}; }
+template <int DT> static int launch_gemv_wide(const WideParams& p, const WidePlan& pl, hipStream_t st) {
+    const dim3 grid(pl.grid), block(64 * WIDE_NW);
+    switch (pl.ng) {
+        case 1: hipLaunchKernelGGL((gemv_wide_kernel<DT, 1>), grid, block, 0, st, p); break;
+        case 2: hipLaunchKernelGGL((gemv_wide_kernel<DT, 2>), grid, block, 0, st, p); break;
+        case 3: hipLaunchKernelGGL((gemv_wide_kernel<DT, 3>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((gemv_wide_kernel<DT, 4>), grid, block, 0, st, p); break;
+    }
+    return launch_status();
+}
+
+extern "C" int bd_binary_linear_decode_wide(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y, int T, int N, int K,
+                                            int64_t sXt, int64_t sAlt, int G, int64_t sYt, int dtype, int out_dtype, int accumulate,
+                                            void* stream) {
+    if (dtype != BD_F16 && dtype != BD_BF16) return BD_E_BAD_DTYPE;
+    if (out_dtype != dtype && out_dtype != BD_F32) return BD_E_BAD_DTYPE;
+    if (T < 0 || T > 64 || N < 0 || K < 0) return BD_E_BAD_SHAPE;
+    if (T == 0) return BD_OK;
+    if (N < 16 || N % 16 || K < 128 || K % 128) return BD_E_BAD_SHAPE;
+    if (G < 1 || N % G) return BD_E_BAD_GROUPS;
+    if (!X || !W || !P || !alpha || !Y) return BD_E_NULL;
+    if (!aligned16(X) || !aligned16(W) || !aligned16(P) || sXt % 8 || sXt < K || sYt < N || sAlt < 0) return BD_E_BAD_SHAPE;
+    const WidePlan pl = wide_plan(T, N);
+    // raw buffer loads: 32-bit byte offsets, bit 31 = "out of range" (bd_gemv_wide.h), so every extent stays below 2 GiB
+    const int64_t lim = 1ll << 31;
+    const int64_t x_bytes = ((int64_t)(T - 1) * sXt + K) * 2, w_bytes = (int64_t)N * K * 2, pg_bytes = w_bytes;      // (16 tenants x 1 bit = 16 bits)
+    if (x_bytes >= lim || w_bytes >= lim || pg_bytes * pl.ng >= lim) return BD_E_BAD_SHAPE;
+    WideParams p{};
+    p.X = (const unsigned short*)X; p.W = (const unsigned short*)W; p.P = (const uint32_t*)P; p.alpha = alpha; p.C = Y;
+    p.T = T; p.N = N; p.K = K; p.gsz = N / G;
+    p.sXt = sXt; p.sCt = sYt; p.sAlt = sAlt;
+    p.accumulate = accumulate ? 1 : 0; p.out_f32 = out_dtype == BD_F32 ? 1 : 0;
+    p.x_bytes = (uint32_t)x_bytes; p.w_bytes = (uint32_t)w_bytes; p.pg_bytes = (uint32_t)pg_bytes; p.p_bytes = (uint32_t)(pg_bytes * pl.ng);
+    return dtype == BD_BF16 ? launch_gemv_wide<DT_BF16>(p, pl, (hipStream_t)stream) : launch_gemv_wide<DT_F16>(p, pl, (hipStream_t)stream);
 }
 
 extern "C" int bd_binary_linear_w8(const void* X, const int8_t* W8, const float* wscale, const int32_t* P, const float* alpha, void* Y,

@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .binary_gemm_kernel import (binary_linear, binary_linear_residual_norm, binary_linear_swiglu, binary_linear_decode, decode_shape_ok, fused_norm_ok, handoff_ok,
-                                 load_decode_masks, pack_decode_masks, tenant_linear, tile_weight)
+                                 load_decode_masks, pack_decode_masks, pack_decode_masks_wide, tenant_linear, tile_weight)
 from ._lib import require_gpu
 from .quant import (cat_gptq4, dequantize_base_gptq4, dequantize_base_int8, pack_gptq4_params, quantize_base_gptq4, quantize_base_int8,
                     tile_weight_gptq4, tile_weight_int8, weight_scale)
@@ -125,7 +125,7 @@ class FusedDeltaLinear(nn.Module):
     tile_decode_weight = True     # keep a tile-major decode copy of the base weight (class switch)
 
     def __init__(self, weights, masks, coeffs, interleave8=False, decode_copies=True, base_int8=False, base_gptq4=False, group_size=128,
-                 gptq4=None, dtype=None, dense_base=True):
+                 gptq4=None, dtype=None, dense_base=True, *, wide_decode=False):
         """decode_copies=False skips the decode-only copies (packed sign words, tile-major base weight): a prefill-only user.
         base_int8=True: the (concatenated, interleaved) base is quantised once to the LLM.int8 vector-wise format (quant.quantize_base_int8); the
         16-bit `weight` becomes the reference-dequantised weight (what bitdelta/misc.py dequantize_model leaves in the model: prefill and every
@@ -140,7 +140,10 @@ class FusedDeltaLinear(nn.Module):
         chunks, scoring); the fused SwiGLU / residual + norm prefill forms are not offered, the layer takes its separate launches.
         base_gptq4="only": the same for the 4-bit base -- the tile-major nibbles and the group parameters are the one resident copy, the
         dequantised 16-bit weight is neither built nor kept, and those launches run bd_binary_linear_q4.  It needs the decode copies
-        (N % 16 == 0, K % 128 == 0, group_size % 128 == 0, at most 16 tenants): ValueError otherwise.  Internally it is dense_base = False."""
+        (N % 16 == 0, K % 128 == 0, group_size % 128 == 0, at most 16 tenants): ValueError otherwise.  Internally it is dense_base = False.
+        wide_decode=True (opt-in; 16-bit base only): a module of 17 .. 64 tenants also keeps `mask_wide` (pack_decode_masks_wide) and the
+        tile-major base weight, and a launch with one row per tenant runs bd_binary_linear_decode_wide -- ONE launch that streams the base
+        once -- instead of binary_linear's chunks of 16 rows.  With 16 tenants or fewer the flag changes nothing."""
         super().__init__()
         if not dense_base and not base_int8:
             raise ValueError("dense_base=False drops the 16-bit base weight: it needs base_int8=True (the int8 bytes are then the only copy)")
@@ -211,6 +214,13 @@ class FusedDeltaLinear(nn.Module):
             self.register_buffer("weight_tiled", tile_weight_gptq4(qw))
         else:
             self.register_buffer("weight_tiled", tile_weight(self.weight) if tiled else None)
+        # ... and, opt-in, of the sign words of MORE than 16 tenants in row groups of 16 (each group a packed t_pad = 16 tensor) for the wide launch
+        wide = bool(wide_decode) and decode_copies and 16 < self.mask.shape[0] <= 64
+        if wide and (self.base_int8 or self.base_gptq4 or N % 16 or K % 128):
+            raise ValueError("wide_decode: 16-bit base weight, N % 16 == 0, K % 128 == 0 (the wide launch has no int8 / 4-bit form)")
+        self.register_buffer("mask_wide", pack_decode_masks_wide(self.mask) if wide else None)
+        if wide and self.weight_tiled is None:
+            self.weight_tiled = tile_weight(self.weight)
 
     @classmethod
     def from_gptq4(cls, triples, masks, coeffs, dtype=torch.float16, interleave8=False, decode_copies=True, only=False):
@@ -225,6 +235,11 @@ class FusedDeltaLinear(nn.Module):
         return self.mask_packed is not None and B == self.mask.shape[0] and B * M <= 16 and \
             decode_shape_ok(B, M, self.N, K, B) and x.data_ptr() % 16 == 0 and \
             x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0 and x.stride(2) == 1
+
+    def _wide_ok(self, x):
+        """the wide launch takes this input: the module keeps mask_wide (wide_decode=True, 17 .. 64 tenants), one aligned row per tenant"""
+        return self.mask_wide is not None and x.shape[0] == self.mask.shape[0] and x.shape[1] == 1 and x.dtype == self.weight_tiled.dtype and \
+            x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and x.stride(2) == 1
 
     def fusable(self, x, swiglu=False):
         """True when forward_fused can take this input: decode shape inside the fused-norm envelope (and an interleaved pair for SwiGLU)"""
@@ -259,6 +274,9 @@ class FusedDeltaLinear(nn.Module):
                                         norm_weight=next_norm if ssq_out is not None else None, xw_out=xw_out, out=out, ssq_scale=ssq_scale,
                                         weight_scale=self._dec_scale(wt), **self._dec_q4(wt))
         assert ssq_out is None and xw_out is None
+        if self._wide_ok(x):
+            return binary_linear_decode(x, self.weight_tiled, self.mask_wide, self.alpha, layout="wide", groups=self.groups, residual=residual,
+                                        weight_tiled=True, out_dtype=out_dtype, out=out)
         if not self.dense_base:
             return self._forward_bytes(x, residual, out_dtype, out)
         return binary_linear(x, self.weight, self.mask, self.alpha, groups=self.groups, residual=residual, out_dtype=out_dtype, out=out)
@@ -338,7 +356,7 @@ class FusedDeltaLinear(nn.Module):
         v.widths, v.interleave8, v.groups = self.widths, self.interleave8, self.groups
         v.weight, v.mask, v.alpha = self.weight, self.mask[t:t + 1], self.alpha[t:t + 1]
         v.alpha_pair = self.alpha_pair[t:t + 1] if self.alpha_pair is not None else None
-        v.wscale = v.group_params = v.mask_packed = v.weight_tiled = None
+        v.wscale = v.group_params = v.mask_packed = v.weight_tiled = v.mask_wide = None
         v.dense_base, v.N, v.K = self.dense_base, self.N, self.K
         if not self.dense_base:       # the bytes are the base: the view carries them (mask_packed stays None, so it never takes a decode launch)
             v.weight_tiled, v.wscale, v.group_params = self.weight_tiled, self.wscale, self.group_params
@@ -374,8 +392,10 @@ class FusedDeltaLinear(nn.Module):
         coeffs = self.check_tenant(t, masks, coeffs)
         require_gpu(self.mask, *masks)
         maps = fused_columns(self.widths, self.interleave8)[1]
+        # (a wide module: tenant t is slot t % 16 of row group t // 16, itself a packed t_pad = 16 tensor)
+        packed, slot = (self.mask_packed, t) if self.mask_wide is None else (self.mask_wide[t // 16], t % 16)
         for m, (off, blk, stride) in zip(masks, maps):
-            load_decode_masks(m if m.stride(1) == 1 else m.contiguous(), mask=self.mask[t], packed=self.mask_packed, slot=t, col_off=off,
+            load_decode_masks(m if m.stride(1) == 1 else m.contiguous(), mask=self.mask[t], packed=packed, slot=slot, col_off=off,
                               col_blk=blk, col_stride=stride)
         alpha, pair = fused_alpha([c.to(self.alpha.device) for c in coeffs], self.widths, self.interleave8)
         self.alpha[t].copy_(alpha[0])
@@ -539,8 +559,10 @@ class TenantDecoder(nn.Module):
     MAX_STATIC_SLOTS = 4        # captured decode-step graphs kept alive at once (LRU over stop-table width x glue switches)
 
     def __init__(self, cfg, tenants, device, dtype, max_len=MAX_PROMPT + 64, eps=1e-5, base_int8=False, base_gptq4=False, rope=None,
-                 kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True):
-        """dense_base=False (with base_int8; not with base_gptq4): the delta Linears keep no 16-bit base -- the int8 bytes are the one resident
+                 kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True, *, wide_decode=False):
+        """wide_decode=True (opt-in, 17 .. 64 tenants, 16-bit base): the delta Linears of a decode step run ONE wide launch each
+        (FusedDeltaLinear(wide_decode=True)) instead of chunks of 16 rows; the glue launches around them are the ones such a step takes today.
+        dense_base=False (with base_int8; not with base_gptq4): the delta Linears keep no 16-bit base -- the int8 bytes are the one resident
         copy and every launch with more than one row per tenant runs the int8 GEMM on them (FusedDeltaLinear(dense_base=False)).
         base_gptq4="only": the same for the 4-bit base -- the nibbles and group parameters are the one resident copy, those launches run the
         4-bit GEMM (FusedDeltaLinear(base_gptq4="only")); base_gptq4=True keeps the dequantised 16-bit weight next to them, as before.
@@ -600,6 +622,7 @@ class TenantDecoder(nn.Module):
         if isinstance(base_gptq4, str) and base_gptq4 != "only":
             raise ValueError('base_gptq4: False, True or "only", got %r' % (base_gptq4,))
         self.dense_base = bool(dense_base)
+        self.wide_decode = bool(wide_decode)
         self.gptq4_only = base_gptq4 == "only"     # the delta Linears keep no 16-bit base either: the nibbles are the one copy
         self.base_gptq4 = bool(base_gptq4)  # ... or a 4-bit GPTQ base (FusedDeltaLinear(base_gptq4=True)); lm_head, embeddings and norms stay 16-bit
         self.base_int8 = bool(base_int8)    # the delta Linears stream an int8 base at decode (FusedDeltaLinear(base_int8=True)); lm_head stays 16-bit
@@ -666,7 +689,7 @@ class TenantDecoder(nn.Module):
     # ---------------------------------------------------------------- construction
     @classmethod
     def synthetic(cls, name, tenants, device, dtype=torch.float16, seed=0, layers=None, max_len=MAX_PROMPT + 64, shared_heads=False, base_int8=False,
-                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True):
+                  base_gptq4=False, rope=None, kv_cache=None, kv_scales=None, sliding_window=None, dense_base=True, *, wide_decode=False):
         """Random weights with the statistics of SURVEY.md section 8(d): W ~ N(0, 0.02^2), fine-tune = W + N(0, (5e-4)^2) per
         tenant (alpha = mean|delta| ~ 4e-4).  Embedding / norm / lm_head are per tenant as in the reference's diff.pt files
         (`shared_heads=True` stores them once and expands -- same arithmetic, used only to keep test models small).  rope, sliding_window: as in
@@ -675,7 +698,7 @@ class TenantDecoder(nn.Module):
         hid, inter, nl, heads, kvh, vocab = cfg
         nl = layers or nl
         self = cls(cfg, tenants, device, dtype, max_len=max_len, base_int8=base_int8, base_gptq4=base_gptq4, rope=rope, kv_cache=kv_cache,
-                   kv_scales=kv_scales, sliding_window=sliding_window, dense_base=dense_base)
+                   kv_scales=kv_scales, sliding_window=sliding_window, dense_base=dense_base, wide_decode=wide_decode)
         gen = torch.Generator(device=device).manual_seed(seed)
         hd = hid // heads
 
@@ -692,7 +715,7 @@ class TenantDecoder(nn.Module):
         def fused(*shapes, interleave8=False):
             parts = [delta_linear(o, i) for o, i in shapes]
             return FusedDeltaLinear([p[0] for p in parts], [p[1] for p in parts], [p[2] for p in parts], interleave8=interleave8, base_int8=base_int8,
-                                    base_gptq4=base_gptq4, dense_base=dense_base)
+                                    base_gptq4=base_gptq4, dense_base=dense_base, wide_decode=wide_decode)
 
         def per_tenant(*shape, scale=None):
             reps = 1 if shared_heads else tenants

@@ -197,6 +197,25 @@ int bd_binary_linear_decode_q4(const void* X, const int32_t* W4, const uint32_t*
                                const void* norm_w, int64_t s_norm, float eps, int epilogue,
                                const float* ssq_in, float* ssq_out, void* xw_out, void* stream);
 
+/* The decode Linear for MORE THAN 16 TENANTS in one launch (up to 64, one activation row each): where bd_binary_linear runs such a batch
+ * as consecutive 16-row launches that each stream the base weight again, this entry streams W once (gemv_wide_kernel, csrc/bd_gemv_wide.h):
+ *     Y[t, n] = round( sum_k X[t,k] W[n,k]  +  alpha[t, g(n)] * sum_k X[t,k] S_t[k,n]  [+ Y_in[t, n]] ),   t = 0 .. T-1, T <= 64
+ * fp32 accumulation, scale_then_add's two roundings and one rounding to out_dtype (dtype or BD_F32), as the packed decode forms.
+ *   X [T, K], row stride sXt elements (16-byte aligned rows); Y [T, N], row stride sYt; accumulate = 1 adds Y's previous contents.
+ *   W: the TILE-MAJOR decode copy of bd_binary_linear_decode (bitdelta_amd.binary_gemm_kernel.tile_weight), 16-byte aligned.
+ *   P: the WIDE packed sign layout (pack_decode_masks_wide), int32 [ceil(T/16)][N/16][K/128][4][16][16]: row group r is, byte for byte, the
+ *      PACKED layout of bd_binary_linear_decode with t_pad = 16 over tenants 16 r .. 16 r + 15 (zero padding past T), so
+ *      bd_tenant_signs_load(packed_dst = P + r * N * K / 2, t_pad = 16, slot = t % 16) replaces one tenant in place.
+ *   alpha: fp32 [T, G], row stride sAlt elements (0 broadcasts one row); G scale groups split N evenly.
+ * One launch, no workspace, no atomics, capturable in a graph, a pure function of its inputs (fixed summation order).
+ * Checked in this order, before any device work: dtype / out_dtype (BD_E_BAD_DTYPE); T < 0, T > 64, N < 0, K < 0 (BD_E_BAD_SHAPE);
+ * T == 0 returns BD_OK; N < 16, N % 16, K < 128, K % 128 (BD_E_BAD_SHAPE); G < 1 or N % G (BD_E_BAD_GROUPS); a NULL operand (BD_E_NULL);
+ * misaligned X / W / P, sXt % 8, sXt < K, sYt < N, sAlt < 0 (BD_E_BAD_SHAPE); an operand extent of 2 GiB or more (BD_E_BAD_SHAPE).
+ * Not offered here: RMSNorm prologue, hand-off, SwiGLU epilogue, int8 / 4-bit base, more than one row per tenant. */
+int bd_binary_linear_decode_wide(const void* X, const void* W, const int32_t* P, const float* alpha, void* Y,
+                                 int T, int N, int K, int64_t sXt, int64_t sAlt, int G, int64_t sYt,
+                                 int dtype, int out_dtype, int accumulate, void* stream);
+
 /* The fused Linear over the INT8 base weight for M >= 2 rows per batch entry (prefill, extend, prefill chunks, scoring): the formula and the
  * bytes of bd_binary_linear_decode_w8 -- W8 is the SAME tile-major decode copy, so an int8 model keeps one copy of its base --
  *     Y[b,m,n] = round( wscale[n] * sum_k X[b,m,k] CB[n,k]  +  alpha[b, g(n)] * sum_k X[b,m,k] S_b[k,n]  [+ Y_in[b,m,n]] )
